@@ -19,13 +19,17 @@ Timing is barrier + synchronize bracketed, max over ranks.  Consecutive pair sol
 pipelined over 2 HIP streams (--streams): a solve's level kernel waits for the previous
 solve's level kernel, and the previous pair's latency-bound tail (levels >= 3, matching,
 stitch) runs beside it; every step still solves its pair completely inside the timed region.
-Every timed solve's stitched maps are kept (on the device) and, after the timed region,
-compared bit for bit with the same pair solved again on one stream, un-pipelined
-(`step_outputs_identical`, `step_outputs`).  The default c3 line also carries `c5_split`:
+With `--full`, every timed solve's stitched maps are kept (on the device) and, after the
+timed region, compared bit for bit with the same pair solved again on one stream, un-pipelined
+(`step_outputs_identical`, `step_outputs`), and the default c3 line also carries `c5_split`:
 one 4096^2 pair per step with its 256 tiles split over the ranks and gathered to rank 0
 (north_star's 8-GPU target), with the N = 1 reference solved on rank 0 in the same run.
 
-Also reported: the roofline of the dominant kernel (dm_corr_level12), timed with HIP
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up, times the N steps
+and prints the result line (metric, value, unit, ms_per_step, ...).  `--dump-outputs DIR`
+also writes the stitched maps the last timed step returned (rank 0's) as DIR/<name>.npy.
+Everything else runs only with `--full`: the step-output check and c5_split above, the
+k-level pass, and the roofline of the dominant kernel (dm_corr_level12), timed with HIP
 events on the launch stream inside the timed steps, the HBM roofline of the level-0
 volume kernel (dm_corr_volume, 4 B/voxel written, and its fp16 variant, 2 B/voxel) on the
 same batch, the fp16 volume's argmax flip rate, and the CPU oracle's rate on a bounded
@@ -70,6 +74,7 @@ ONE_DEVICE = os.environ.get('DM_BENCH_ONE_DEVICE', '0') == '1'
 VOLUME_BUDGET = 72e9           # bytes of level-0 volume materialised for its roofline: the whole
                                # C3 batch in float32 (68.7 GB), 8 S=256 tiles in fp16 (whole
                                # rounds of workgroups over the chip, as C5's 256 tiles are)
+DUMP_BUDGET = 64 << 20         # bytes --dump-outputs writes at most (larger outputs are sampled)
 
 
 def parse():
@@ -77,6 +82,14 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=5)   # the clock settles after ~3 launches
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline figure: the step-output check, the '
+                         'k-level pass, the kernel rooflines, the fp16 flip rate, the CPU baseline and '
+                         'the c5_split sub-line (each still switched off by its own --no-... option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the stitched maps the last timed step returned (rank 0's, float64) as "
+                         'DIR/<name>.npy; above %d MB in all, a fixed seeded sample of each map'
+                         % (DUMP_BUDGET >> 20))
     ap.add_argument('--streams', type=int, default=2,
                     help='HIP streams consecutive pair solves are pipelined over (1: no overlap)')
     ap.add_argument('--level-stream', type=int, default=0,
@@ -608,9 +621,10 @@ class Pipeline:
             if hold is not None and res is not None:
                 hold.append((i, res))
 
-    def run(self, steps, warmup, timed=True, hold=None):
+    def run(self, steps, warmup, timed=True, hold=None, last=None):
         """warmup untimed steps, then `steps` timed ones bracketed by barrier + synchronize;
-        seconds, max over ranks"""
+        seconds, max over ranks.  last: list that receives what `hold` would, of the last
+        timed step only."""
         import torch.distributed as tdist
         for _ in range(warmup):
             self.step()
@@ -619,8 +633,13 @@ class Pipeline:
             tdist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        for _ in range(steps):
-            self.step(timed=timed, hold=hold)
+        for k in range(steps):
+            final = last is not None and k == steps - 1
+            h = hold if hold is not None else (last if final else None)
+            n0 = len(h) if h is not None else 0
+            self.step(timed=timed, hold=h)
+            if final and h is not last:
+                last.extend(h[n0:])
         torch.cuda.synchronize()
         if self.dist:
             tdist.barrier()
@@ -644,6 +663,25 @@ def _sha256(maps):
     for t in maps:
         h.update(t.cpu().numpy().tobytes())
     return h.hexdigest()
+
+
+def dump_outputs(path, last, pair_idx):
+    """--dump-outputs: the stitched (d_map, out_map) every solve of the last timed step
+    returned on this rank, as path/pair<index>_<map>.npy (float64, NaN where no tile covers a
+    cell).  Whole maps while they fit DUMP_BUDGET in all; otherwise the same number of cells
+    of every map, at flat indices drawn once from a fixed seed (sorted, the same from run to
+    run), as a 1-D array."""
+    os.makedirs(path, exist_ok=True)
+    maps = [('pair%04d_%s' % (pair_idx[i], nm), t)
+            for i, res in last for nm, t in zip(('d_map', 'out_map'), res)]
+    total = sum(t.numel() * t.element_size() for _, t in maps)
+    per_map = DUMP_BUDGET // (8 * max(1, len(maps))) if total > DUMP_BUDGET else None
+    rng = np.random.default_rng(20240607)
+    for name, t in maps:
+        if per_map is not None and t.numel() > per_map:
+            idx = np.sort(rng.choice(t.numel(), size=per_map, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + '.npy'), t.cpu().numpy())
 
 
 def check_step_outputs(held, solvers, dist, steps):
@@ -790,8 +828,9 @@ def main():
     pipe = Pipeline(solvers, dev, dist, nstreams=nstreams, chain_levels=args.chain_levels,
                     level_stream=args.level_stream, stats_stream=args.stats_stream,
                     priority=-1 if args.pair_priority == 'high' else 0)
-    held = [] if not args.no_step_check else None
-    elapsed = pipe.run(args.steps, args.warmup, hold=held)
+    held = [] if (args.full and not args.no_step_check) else None
+    last = [] if args.dump_outputs else None
+    elapsed = pipe.run(args.steps, args.warmup, timed=args.full, hold=held, last=last)
     ms_step = elapsed / args.steps * 1e3
     value = job_pairs * args.steps * voxels / elapsed / 1e9
     l1_ms = solver.level1_ms() if solver else None
@@ -800,13 +839,17 @@ def main():
     # the timed solves' outputs, checked after the timed region
     step_check = check_step_outputs(held, solvers, dist, args.steps) if held is not None else None
     del held
+    if last is not None:
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last, pair_idx)
+        del last
 
     # BASELINE.json states C2 / C3 (/ C4) on a 3- / 4-level pyramid: the same timed run with
     # the pyramid cut to k levels (levels 0..k-1 built, matching starts at level k-1), next to
     # the full pyramid Correlation_map always builds
     k_level = None
     k = BASELINE_LEVELS.get(args.config)
-    if args.levels is None and k and not args.no_k_level and not split:
+    if args.full and args.levels is None and k and not args.no_k_level and not split:
         for s_ in solvers:
             s_.levels = k
         el_k = pipe.run(args.steps, 1, timed=False)
@@ -818,7 +861,7 @@ def main():
                    'note': 'same workload and timing, pyramid cut to %d levels (co_map_list[:%d], '
                            'N_map = %d)' % (k, k, 2 ** (k - 1))}
 
-    breakdown = split_breakdown(solver, rank, world, dev) if split else None
+    breakdown = split_breakdown(solver, rank, world, dev) if (split and args.full) else None
     # (every rank decides alike: the re-solve below is collective for the c5 split)
     out_hash = step_check['sha256'] if step_check else None
     if args.output_hash and step_check is None:
@@ -828,7 +871,6 @@ def main():
             out_hash = _sha256(res)
 
     if rank == 0:
-        roof = level_roofline(solver, tile, l1_ms)
         lv = ('%d-level pyramid' % args.levels) if args.levels else 'full pyramid'
         if args.config == 'c4':
             workload = ('C4: batch of %d independent %dx%d pairs per step (%dx%d tiles of S=%d each), '
@@ -858,9 +900,10 @@ def main():
                           'pairs_per_gpu_per_step': per_gpu, 'parallelism': par,
                           'streams': nstreams, 'level_stream': bool(args.level_stream),
                           'stats_stream': bool(args.stats_stream and args.level_stream),
-                          'pair_priority': args.pair_priority, 'chain_levels': bool(args.chain_levels)},
-               'roofline': roof,
-               'level_kernel_volume_equivalent': volume_equivalent(solver, tile, l1_ms)}
+                          'pair_priority': args.pair_priority, 'chain_levels': bool(args.chain_levels)}}
+        if args.full:
+            rec['roofline'] = level_roofline(solver, tile, l1_ms)
+            rec['level_kernel_volume_equivalent'] = volume_equivalent(solver, tile, l1_ms)
         if step_check is not None:
             rec['step_outputs_identical'] = step_check['identical']
             rec['step_outputs'] = step_check
@@ -874,17 +917,18 @@ def main():
             rec['output_sha256'] = out_hash
         if breakdown:
             rec['split_breakdown'] = breakdown
-        if not args.no_volume:
+        if args.full and not args.no_volume:
             rec['volume_kernel_roofline'] = volume_roofline(solver)
             rec['volume_f16_kernel_roofline'] = volume_roofline(solver, f16=True)
             if world == 1:
                 rec['fp16_flip_rate'] = fp16_flip_rate(solver)
-        if world == 1 and not args.no_cpu_baseline and tile <= 128:   # S=256: 17 GB level 0 per tile on the host
+        if args.full and world == 1 and not args.no_cpu_baseline and tile <= 128:   # S=256: 17 GB level 0 per tile on the host
             rec['cpu_baseline'] = cpu_baseline(args.cpu_sample_tiles, tile)
 
     # north_star's "tiled 4096^2 pairs, 8 GPUs" line, carried by the default (c3) run, so the
     # driver's `bench.py --gpus N` measures it at every N (all ranks take part)
-    if args.config == 'c3' and not args.no_c5_split and args.tile is None and args.grid is None:
+    if (args.full and args.config == 'c3' and not args.no_c5_split and args.tile is None
+            and args.grid is None):
         del pipe
         torch.cuda.empty_cache()
         own_group = False

@@ -91,6 +91,33 @@ def test_store_ceiling_follows_the_instance_pattern(bench):
     assert bench.store_ceiling(64, 64, 2, 5000.0) is None
 
 
+def test_dump_outputs_whole_or_fixed_sample(bench, monkeypatch, tmp_path):
+    """--dump-outputs: whole float64 maps within the budget; above it the same seeded sample
+    of every map on every run, within the budget in all."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(5)
+    last = [(i, (torch.rand((1, 40, 50), generator=g, dtype=torch.float64),
+                 torch.rand((40, 50), generator=g, dtype=torch.float64))) for i in range(2)]
+    last[0][1][1][0, 0] = float('nan')
+    bench.dump_outputs(str(tmp_path / 'whole'), last, [3, 7])
+    names = ['pair0003_d_map.npy', 'pair0003_out_map.npy', 'pair0007_d_map.npy', 'pair0007_out_map.npy']
+    assert sorted(os.listdir(tmp_path / 'whole')) == names
+    got = np.load(tmp_path / 'whole' / names[1])
+    assert got.dtype == np.float64 and np.array_equal(got, last[0][1][1].numpy(), equal_nan=True)
+    monkeypatch.setattr(bench, 'DUMP_BUDGET', 4 * 8 * 100)      # 100 cells per map
+    bench.dump_outputs(str(tmp_path / 'a'), last, [3, 7])
+    bench.dump_outputs(str(tmp_path / 'b'), last, [3, 7])
+    total = 0
+    for nm in names:
+        a, b = np.load(tmp_path / 'a' / nm), np.load(tmp_path / 'b' / nm)
+        assert a.shape == (100,) and np.array_equal(a, b, equal_nan=True)
+        total += a.nbytes
+    assert total <= bench.DUMP_BUDGET
+    src = last[1][1][0].numpy().ravel()
+    assert np.isin(np.load(tmp_path / 'a' / names[2]), src).all()
+
+
 def test_roofline_work_derivation(bench, monkeypatch):
     """roofline.work: MAC slots from the PMC MFMA math-op counter and pow
     evaluations from the float64 FMA count, each against the algorithmic count; present only

@@ -20,7 +20,7 @@ def _bench(*args, timeout=150):
            if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(DM_BENCH_BACKEND='gloo', DM_BENCH_ONE_DEVICE='1', OMP_NUM_THREADS='4')
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', '1', '--warmup', '1',
-                          '--no-volume', '--no-cpu-baseline'] + list(args),
+                          '--full', '--no-volume', '--no-cpu-baseline'] + list(args),
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]

@@ -4,8 +4,8 @@ bench.py times pair solves pipelined over 2 (or 3) HIP streams, each solve's lev
 event-chained to the previous one's (or, with --chain-levels 0, overlapping it), buffers
 crossing streams through record_stream.  bench.py keeps every timed solve's stitched maps on
 the device and, after the timed region, compares each bit for bit with the same pair solved
-again on one stream, un-pipelined (`step_outputs`).  These tests run bench.py itself (a
-subprocess, the driver's command line) and check that:
+again on one stream, un-pipelined (`step_outputs`, part of `bench.py --full`).  These tests
+run `bench.py --full` itself (a subprocess) and check that:
 
   * every timed solve is identical to the un-pipelined solve (`step_outputs_identical`);
   * that solve's sha256 equals the single-stream engine path of tests/test_c3_batch.py --
@@ -38,7 +38,7 @@ pytestmark = pytest.mark.gpu
 def _bench(*args, timeout=170):
     env = {k: v for k, v in os.environ.items()
            if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
-    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--no-volume',
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--full', '--no-volume',
                           '--no-cpu-baseline', '--no-k-level'] + list(args),
                          cwd=REPO, env=env, capture_output=True, text=True, timeout=timeout)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -87,6 +87,34 @@ def test_timed_steps_match_single_stream(config, S, streams, chain):
                  '--chain-levels', str(chain), '--no-c5-split')
     assert rec['config']['streams'] == streams and rec['config']['chain_levels'] == bool(chain)
     _check(rec, 6, _single_stream_sha(S))
+
+
+def test_plain_run_is_lean_and_dumps_its_last_step(tmp_path):
+    """Without --full the line carries the headline figure only, and --dump-outputs writes the
+    stitched maps of the last timed step: bit for bit the single-stream engine path's."""
+    env = {k: v for k, v in os.environ.items()
+           if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+    out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--config', 'c2',
+                          '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / 'out')],
+                         cwd=REPO, env=env, capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    rec = json.loads(lines[0])
+    assert rec['steps'] == 3 and rec['ms_per_step'] > 0 and rec['value'] > 0
+    assert rec['unit'] == 'Gvox/s' and rec['higher_is_better'] is True and rec['dtype']
+    for key in ('step_outputs', 'roofline', 'k_level', 'c5_split', 'cpu_baseline',
+                'volume_kernel_roofline', 'fp16_flip_rate'):
+        assert key not in rec, key
+    assert sorted(os.listdir(tmp_path / 'out')) == ['pair0000_d_map.npy', 'pair0000_out_map.npy']
+    d_map = np.load(tmp_path / 'out' / 'pair0000_d_map.npy')
+    out_map = np.load(tmp_path / 'out' / 'pair0000_out_map.npy')
+    assert d_map.dtype == np.float64 and d_map.shape == (1, GRID * 64, GRID * 64)
+    assert out_map.dtype == np.float64 and out_map.shape == (GRID * 64, GRID * 64)
+    h = hashlib.sha256()
+    h.update(d_map.tobytes())
+    h.update(out_map.tobytes())
+    assert h.hexdigest() == _single_stream_sha(64)
 
 
 def test_c4_full_size_share():

@@ -6,7 +6,7 @@ set -uo pipefail
 REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 for pass in 1 2; do
   for lib in "$@"; do
-    DM_LIB_PATH=$lib timeout -k 10 200 python3 "$REPO/bench.py" --config c5 --steps 3 --warmup 1 --no-cpu-baseline \
+    DM_LIB_PATH=$lib timeout -k 10 200 python3 "$REPO/bench.py" --full --config c5 --steps 3 --warmup 1 --no-cpu-baseline \
         --no-volume --no-k-level > /tmp/c5ab.json 2> /tmp/c5ab.err || { echo "$lib failed"; tail -3 /tmp/c5ab.err; exit 1; }
     python3 - "$lib" "$pass" <<'PY'
 import json, sys

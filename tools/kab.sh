@@ -15,7 +15,7 @@ for pass in 1 2; do
     lib=${ent%%+*}; envs=${ent#"$lib"}; envs=${envs//+/ }
     b=$(basename "$lib" .so)$(echo "$envs" | tr ' =' '_-')
     env $envs DM_LIB_PATH=$lib timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${b}_$pass" -o run -- \
-        python3 "$REPO/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-volume > "$OUT/${b}_$pass.json" 2> "$OUT/${b}_$pass.err"
+        python3 "$REPO/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-volume > "$OUT/${b}_$pass.json" 2> "$OUT/${b}_$pass.err"
     python3 - "$OUT/${b}_$pass" "$b pass $pass" <<'PY'
 import csv, glob, json, sys
 d, tag = sys.argv[1], sys.argv[2]

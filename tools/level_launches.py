@@ -23,7 +23,7 @@ def main(root, bench, label):
     warm, steps = d['warmup'], d['steps']
     ms = [(e - s) * 1e-6 for s, e, _ in rows]
     timed = ms[warm:warm + steps]
-    print('%s, full C3 grid, rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline (%s)'
+    print('%s, full C3 grid, rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline (%s)'
           % (rows[0][2] if rows else '?', label))
     print('launch durations (ms), in order (%d warm-up, %d timed, then the k_level line and the volume checks): %s'
           % (warm, steps, ', '.join('%.3f' % m for m in ms)))

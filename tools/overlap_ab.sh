@@ -13,7 +13,7 @@ for pass in $(seq 1 ${1:-2}); do
     for v in "1 2" "0 2" "0 3"; do
       set -- $v
       echo "== pass $pass $cfg chain-levels $1 streams $2"
-      timeout -k 10 120 python3 "$REPO/bench.py" --config $cfg --chain-levels $1 --streams $2 --no-cpu-baseline --no-volume --no-k-level 2>/dev/null | line || exit 1
+      timeout -k 10 120 python3 "$REPO/bench.py" --full --config $cfg --chain-levels $1 --streams $2 --no-cpu-baseline --no-volume --no-k-level 2>/dev/null | line || exit 1
     done
   done
 done

@@ -9,7 +9,7 @@ REPO=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-BENCH="$REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline"
+BENCH="$REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -o run -- \
     python3 $BENCH > "$OUT/bench.json" 2> "$OUT/stats.err"
 python3 "$REPO/tools/kstats.py" "$OUT/stats" > "$OUT/kernel_stats_by_grid.csv"

@@ -78,6 +78,9 @@ SIGNATURES = {
     'dm_stitch': ([_P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, _P, _P, _P],
                   ctypes.c_int),
     'dm_seq_sum': ([_P, ctypes.c_int64, _P, _P], ctypes.c_int),
+    'dm_fb_check': ([_P, _P, _I, _I, _I, ctypes.c_double, _P, _P, _P], ctypes.c_int),
+    'dm_stitch_fb': ([_P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.c_double,
+                      _P, _P, _P, _P], ctypes.c_int),
 }
 
 _lib = None

@@ -504,6 +504,104 @@ def solve_tiles(img1, img2, origins, h0, w0, ws, method, sub_pix=True, filtering
     return out
 
 
+def bidir_origins(origins, H):
+    """Tile origins of a bidirectional solve on the row-stacked pair (solve_tiles_bidir):
+    int64 [2T][2], the T origins followed by the same origins with ``H`` (the rows of one
+    image) added to the row.  A pure host function."""
+    org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+    return np.concatenate([org, org + np.array([int(H), 0], dtype=np.int64)], axis=0)
+
+
+def stack_pair(img1, img2):
+    """(A, Bk) = (img1 over img2, img2 over img1), stacked along rows: tile t of (A, Bk) at
+    bidir_origins(...)[t] is the forward crop pair (img1, img2) for t < T and the backward one
+    (img2, img1) for t >= T.  Each crop lies inside its own image, so none straddles the seam.
+    Tensors stay tensors (on their device), anything else becomes a numpy array."""
+    if isinstance(img1, torch.Tensor) or isinstance(img2, torch.Tensor):
+        a, b = torch.as_tensor(img1), torch.as_tensor(img2)
+        if a.shape != b.shape or a.dim() != 2:
+            raise ValueError('img1 and img2 must have the same 2-D shape')
+        b = b.to(a.device)
+        return torch.cat([a, b], 0), torch.cat([b, a], 0)
+    a, b = np.asarray(img1), np.asarray(img2)
+    if a.shape != b.shape or a.ndim != 2:
+        raise ValueError('img1 and img2 must have the same 2-D shape')
+    return np.concatenate([a, b], 0), np.concatenate([b, a], 0)
+
+
+def solve_tiles_bidir(img1, img2, origins, h0, w0, ws, method, sub_pix=True, filtering=False,
+                      filter_window_size=3, filtering_num=3, filtering_mode='median',
+                      device=None, mem_budget=None, stream=None):
+    """solve_tiles in both directions -> (fwd, bwd), each float64 [T][3][h0][w0]: fwd equals
+    solve_tiles(img1, img2, ...) and bwd solve_tiles(img2, img1, ...) bit for bit.  Both
+    directions go through ONE tile stream of 2T tiles on the row-stacked pair (stack_pair,
+    bidir_origins), with solve_tiles' chunking, so every kernel launch covers both
+    directions.  The kernels are unchanged: a tile's result depends only on its own crops."""
+    device = device or default_device()
+    with _on(stream):
+        a = to_device_u8(img1, device)
+        b = to_device_u8(img2, device)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        A, Bk = stack_pair(a, b)
+        org = np.asarray(origins, dtype=np.int64).reshape(-1, 2)
+        T = len(org)
+        both = solve_tiles(A, Bk, bidir_origins(org, a.shape[0]), h0, w0, ws, method, sub_pix, filtering,
+                           filter_window_size, filtering_num, filtering_mode, device=device,
+                           mem_budget=mem_budget)
+    return both[:T], both[T:]
+
+
+def _fb_pair(fwd, bwd):
+    if not (isinstance(fwd, torch.Tensor) and isinstance(bwd, torch.Tensor) and fwd.is_cuda and bwd.is_cuda):
+        raise ValueError('fwd and bwd must be device (cuda) tensors')
+    if fwd.shape != bwd.shape or fwd.dtype != torch.float64 or bwd.dtype != torch.float64:
+        raise ValueError('fwd and bwd must be float64 tensors of one shape')
+    f = (fwd if fwd.dim() == 4 else fwd[None]).contiguous()
+    b = (bwd if bwd.dim() == 4 else bwd[None]).contiguous()
+    if f.dim() != 4 or f.shape[1] != 3:
+        raise ValueError('fwd and bwd must be [T][3][h][w] or [3][h][w]')
+    return f, b
+
+
+def fb_check(fwd, bwd, tol, masked=True, stream=None):
+    """Forward-backward consistency check (dm_fb_check) of matches fwd (img1 -> img2) and bwd
+    (img2 -> img1), float64 device tensors [T][3][h][w] or [3][h][w] -> (err, masked map or
+    None).  err [T][h][w]: each cell's distance from where the walk there (fwd, rounded to
+    the grid) and back (bwd) returns, NaN for an off-tile or non-finite match.  The masked
+    map is fwd with rows 0 and 1 NaN where not err <= tol, the score row unchanged."""
+    f, b = _fb_pair(fwd, bwd)
+    T, _, h, w = f.shape
+    with _on(stream):
+        err = torch.empty((T, h, w), dtype=torch.float64, device=f.device)
+        m = torch.empty_like(f) if masked else None
+        L.check(L.load().dm_fb_check(L.ptr(f), L.ptr(b), T, h, w, float(tol), L.ptr(err), L.ptr(m),
+                                     L.stream_handle()), 'dm_fb_check')
+    if fwd.dim() == 4:
+        return err, m
+    return err[0], (m[0] if m is not None else None)
+
+
+def stitch_fb(fwd, bwd, n, h0, w0, stride, modes, tol, stream=None):
+    """stitch(fb_check(fwd, bwd, tol) masked map) in one kernel (dm_stitch_fb) ->
+    (d_map, out_map, err): d_map NaN at cells that fail the check, out_map unchanged, err
+    [H][W] the stitched round-trip error (NaN where no tile covers)."""
+    mode_ids = [L.CAL_MODES[m] for m in modes]
+    Hout, Wout = stride[0] * (n[0] - 1) + h0, stride[1] * (n[1] - 1) + w0
+    f, b = _fb_pair(fwd, bwd)
+    if tuple(f.shape) != (n[0] * n[1], 3, h0, w0):
+        raise ValueError('fwd / bwd must be [%d][3][%d][%d]' % (n[0] * n[1], h0, w0))
+    with _on(stream):
+        dmap = torch.empty((len(modes), Hout, Wout), dtype=torch.float64, device=f.device)
+        score = torch.empty((Hout, Wout), dtype=torch.float64, device=f.device)
+        err = torch.empty((Hout, Wout), dtype=torch.float64, device=f.device)
+        arr = (ctypes.c_int32 * max(1, len(mode_ids)))(*mode_ids)
+        L.check(L.load().dm_stitch_fb(L.ptr(f), L.ptr(b), n[0], n[1], h0, w0, stride[0], stride[1], arr,
+                                      len(mode_ids), float(tol), L.ptr(dmap), L.ptr(score), L.ptr(err),
+                                      L.stream_handle()), 'dm_stitch_fb')
+    return dmap, score, err
+
+
 def stitch(match, n, h0, w0, stride, modes, stream=None):
     """ImageCutSolver._execute_matching stitching on the device -> (d_map, out_map)."""
     mode_ids = [L.CAL_MODES[m] for m in modes]

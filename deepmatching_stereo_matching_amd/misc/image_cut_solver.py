@@ -29,7 +29,8 @@ class ImageCutSolver():
         filtering=False,
         filtering_window_size=3,
         filtering_num=3,
-        filtering_mode='average'
+        filtering_mode='average',
+        consistency=None
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -58,6 +59,9 @@ class ImageCutSolver():
         self.filtering_window_size = filtering_window_size
         self.filtering_num = filtering_num
         self.filtering_mode = filtering_mode
+        # forward-backward consistency tolerance in pixels (None: the reference's behaviour)
+        self.consistency = consistency
+        self.consistency_map = None
 
         self.log_flg = True
 
@@ -117,7 +121,8 @@ class ImageCutSolver():
         chunk's results gathered to rank 0 behind the compute, rank 0 stitches -- and the maps
         come back on every rank (one broadcast; tile_sharding(result='root'): rank 0 only, the
         others get None).  Every rank must then solve the same pair (shard.broadcast_pair
-        sends it from rank 0)."""
+        sends it from rank 0).  With self.consistency set both branches solve the pair in both
+        directions and return a third tensor, the stitched round-trip error (engine.stitch_fb)."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -134,7 +139,11 @@ class ImageCutSolver():
                                              L.METHODS[self.feature_name], self.degree_map_mode,
                                              self.sub_pix, self.filtering, self.filtering_window_size,
                                              self.filtering_num, self.filtering_mode,
-                                             result=shard.shard_result(), grid=(n, origins))
+                                             result=shard.shard_result(), grid=(n, origins),
+                                             consistency=self.consistency)
+        if self.consistency is not None:
+            fwd, bwd = engine.solve_tiles_bidir(*args)
+            return engine.stitch_fb(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency)
         match = engine.solve_tiles(*args)
         return engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
 
@@ -142,10 +151,13 @@ class ImageCutSolver():
         """
         小画像ごとにマッチングを行い結果を結合
         """
-        d_map, out_map = self._execute_matching_device()
+        maps = self._execute_matching_device()
+        d_map, out_map = maps[0], maps[1]
         # (None on the ranks other than 0 of a sharded solve with tile_sharding(result='root'))
         self.d_map = d_map.cpu().numpy() if d_map is not None else None
         self.out_map = out_map.cpu().numpy() if out_map is not None else None
+        if self.consistency is not None:   # [H][W] round-trip error; d_map is NaN where it exceeds the tolerance
+            self.consistency_map = maps[2].cpu().numpy() if maps[2] is not None else None
 
     def __call__(self):
         self._cut_and_pool()

@@ -382,36 +382,54 @@ def solve_tiles_sharded(img1, img2, origins, h0, w0, ws, method, sub_pix=True, f
 def solve_image_sharded(img1, img2, image_size, stride, window_size, method, modes=('elevation',),
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
                         filtering_mode='average', device=None, solver=None, stitcher=None,
-                        result='all', chunks=4, grid=None):
+                        result='all', chunks=4, grid=None, consistency=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
     (``'root'``: the others get (None, None)).  ``grid``: (tile counts, origins) when the caller
-    counted them itself (ImageCutSolver counts on the shape before _padding, :46,58-62)."""
+    counted them itself (ImageCutSolver counts on the shape before _padding, :46,58-62).
+    ``consistency``: a tolerance in pixels; the pair is then solved in both directions -- the
+    BandSolver runs on the row-stacked pair with 2T origins (engine.stack_pair, bidir_origins),
+    so the bands, chunks and gathers are the one-direction ones over twice the tiles -- and rank
+    0 splits the gathered tiles and stitches with the forward-backward check fused in
+    (engine.stitch_fb, or ``stitcher(fwd, bwd, n, h0, w0, stride, modes, tol)``) ->
+    (d_map, out_map, err [H][W]) under the same ``result`` rules ((None, None, None) off root)."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
+    nmaps = 2
+    if consistency is not None:
+        nmaps = 3
+        T = len(np.asarray(origins).reshape(-1, 2))
+        origins = engine.bidir_origins(origins, np.shape(img1)[0])
+        img1, img2 = engine.stack_pair(img1, img2)
     band = BandSolver(img1, img2, origins, image_size[0], image_size[1], window_size, method, device=device,
                       chunks=chunks, dst=0, solver=solver)
     match = band.solve(sub_pix=sub_pix, filtering=filtering, filter_window_size=filter_window_size,
                        filtering_num=filtering_num, filtering_mode=filtering_mode)
-    stitch = stitcher or engine.stitch
-    maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes)) if match is not None else None
+    if match is None:
+        maps = None
+    elif consistency is not None:
+        stitch = stitcher or engine.stitch_fb
+        maps = stitch(match[:T], match[T:], n, image_size[0], image_size[1], stride, list(modes), consistency)
+    else:
+        stitch = stitcher or engine.stitch
+        maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
     if not _group() or world()[1] == 1:
         return maps
     if result == 'root':
-        return maps if maps is not None else (None, None)
+        return maps if maps is not None else (None,) * nmaps
     H = stride[0] * (n[0] - 1) + image_size[0]
     W = stride[1] * (n[1] - 1) + image_size[1]
     dev = band.device
     if maps is None:
-        d = torch.empty((len(modes), H, W), dtype=torch.float64, device=dev)
-        o = torch.empty((H, W), dtype=torch.float64, device=dev)
+        out = [torch.empty((len(modes), H, W), dtype=torch.float64, device=dev)]
+        out += [torch.empty((H, W), dtype=torch.float64, device=dev) for _ in range(nmaps - 1)]
     else:
-        d, o = (torch.as_tensor(m) for m in maps)
-    _bcast(d, 0)
-    _bcast(o, 0)
-    return d, o
+        out = [torch.as_tensor(m) for m in maps]
+    for t in out:
+        _bcast(t, 0)
+    return tuple(out)
 
 
 def solve_pairs_sharded(pairs, fn):

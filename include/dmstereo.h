@@ -215,6 +215,38 @@ int dm_stitch(const double *d_match, int32_t n0, int32_t n1, int32_t h0, int32_t
               int32_t stride0, int32_t stride1, const int32_t *modes, int32_t nmodes,
               double *d_dmap, double *d_score, void *stream);
 
+/* ---- Forward-backward consistency check (dm_fb.hip) -------------------------------------
+ * Not in the reference, whose only confidence signal is map[2] (level 0 is min-max
+ * normalised per patch, so every patch's best match scores 1.0).  d_fwd holds the tiles of
+ * img1 matched into img2, d_bwd img2 matched into img1: both float64 [T][3][h][w] as dm_match
+ * writes them, tile-local coordinates, the same crop window in both images
+ * (ImageCutSolver._cut_and_pool, image_cut_solver.py:95-113).  For tile t, cell (i, j), in
+ * float64 without contraction:
+ *   qi = floor(F[t,0,i,j] + 0.5);  qj = floor(F[t,1,i,j] + 0.5)
+ *   err = NaN                                         unless 0 <= qi < h and 0 <= qj < w
+ *   err = || B[t,0:2,qi,qj] - (i, j) ||               otherwise
+ *   valid = err <= tol                                (false for NaN)
+ * The range test is made on the doubles before any conversion to int: NaN, +-inf and
+ * off-tile matches give err = NaN and are never used as an index. */
+
+/* The check on T tiles: d_err [T][h][w] receives err; d_masked ([T][3][h][w], may be NULL)
+ * the forward map with rows 0 and 1 set to NaN at invalid cells and row 2 (the score)
+ * copied.  d_masked may equal d_fwd (masking in place: a thread reads only its own forward
+ * cell); d_err must not overlap the inputs.  tol >= 0, +inf allowed (DM_ERR_ARG for a
+ * negative or NaN tolerance). */
+int dm_fb_check(const double *d_fwd, const double *d_bwd, int32_t T, int32_t h, int32_t w,
+                double tol, double *d_err, double *d_masked, void *stream);
+
+/* dm_stitch of the forward tiles with the check fused in: each output pixel picks its tile
+ * by dm_stitch's rule (later tiles overwrite earlier ones), evaluates the check at its tile
+ * cell, and writes every d_dmap mode as NaN where the cell is invalid and as dm_stitch's
+ * value otherwise, d_score = map[2] unchanged, and d_err [Hout][Wout] = err.  Output cells
+ * no tile covers are NaN in all three.  Equals dm_fb_check (masked) followed by dm_stitch. */
+int dm_stitch_fb(const double *d_fwd, const double *d_bwd, int32_t n0, int32_t n1, int32_t h0,
+                 int32_t w0, int32_t stride0, int32_t stride1, const int32_t *modes,
+                 int32_t nmodes, double tol, double *d_dmap, double *d_score, double *d_err,
+                 void *stream);
+
 /* ---- Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -295,7 +327,8 @@ const char *dm_last_error(void);
  * 4-tile column groups of dm_corr_stats' window operands at S = 128 / 256, 1.7 dm_seq_sum,
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
- * dm_pow14_variant). */
+ * dm_pow14_variant).  dm_fb_check and dm_stitch_fb are additive entries within 1.10: no
+ * existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);
 
 #ifdef __cplusplus

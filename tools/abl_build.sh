@@ -152,7 +152,7 @@ PY
     base) ;;
     *) echo "unknown $v"; exit 2 ;;
   esac
-  (cd $d && /opt/rocm/bin/hipcc $FLAGS $EXTRA -I $r/include csrc/dm_kernels.hip csrc/dm_postproc.hip -o $REPO/ab/libdm_$v.so) &
+  (cd $d && /opt/rocm/bin/hipcc $FLAGS $EXTRA -I $r/include csrc/dm_kernels.hip csrc/dm_postproc.hip csrc/dm_fb.hip -o $REPO/ab/libdm_$v.so) &
 done
 wait
 ls -la $REPO/ab

@@ -467,9 +467,30 @@ def tile_bytes(h0, w0, level1=True):
 
 def level1_stored():
     """Does a DevicePyramid of the current configuration store level 1 (DM_FUSE_L2 != 2)?  The
-    fused level kernel (mode 2) keeps it on chip; a shape it does not take stores it anyway, so
-    callers sizing memory for such shapes keep tile_bytes' default."""
+    fused level kernel (mode 2) keeps it on chip; a shape it does not take (level12_fused)
+    stores it anyway, so callers sizing memory for such shapes keep tile_bytes' default."""
     return int(os.environ.get('DM_FUSE_L2', str(FUSE_DEFAULT))) != 2
+
+
+def build_config():
+    """The library's compile-time switches (dm_build_config()) as a dict of ints."""
+    cfg = L.load().dm_build_config().decode()
+    return {k: int(v) for k, v in (kv.split('=') for kv in cfg.split())}
+
+
+def level12_fused(h0, w0, ws):
+    """Does the fused level kernel (dm_corr_level12) take tiles of this shape, so that a
+    DevicePyramid in mode 2 never stores level 1?  The library's own rule, restated:
+    mf16_eligible (csrc/dm_mfma.h: h0 % 4 == 0, w0 a power of two in 32 .. 256, ws <= 15) and,
+    on the three GW = 4 instances (ws <= 5, w0 = 64 / 128 / 256: launch_mfq_t in
+    csrc/dm_kernels.hip), cell blocks per tile a multiple of the NB cell blocks a workgroup
+    holds -- NB read from the loaded library's build configuration, not assumed."""
+    if not (h0 > 0 and h0 % 4 == 0 and w0 in (32, 64, 128, 256) and 1 <= ws <= 15 and ws % 2 == 1):
+        return False
+    if ws > 5 or w0 == 32:      # GW = 2 instances: one cell block per workgroup
+        return True
+    nb = build_config()[{64: 'C2_NB', 128: 'C3_NB', 256: 'C5_NB'}[w0]]
+    return ((h0 // 4) * (w0 // 4)) % nb == 0
 
 
 def _on(stream):

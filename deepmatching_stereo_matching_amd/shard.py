@@ -307,9 +307,9 @@ class BandSolver:
         # chunk's pyramid fits the memory budget; the same count on every rank (the longest band)
         per = max(len(rank_band(self.T, r, self.size)) for r in range(self.size))
         budget = int(mem_budget if mem_budget is not None else os.environ.get('DM_MEM_BUDGET', 64 << 30))
-        # (the fused level kernel keeps level 1 on chip at the MFMA shapes the band sizes take:
-        # w0 a multiple of 64 and ws <= 5; otherwise the pyramid stores it and the estimate keeps it)
-        fused = not engine.level1_stored() and w0 % 64 == 0 and h0 % 4 == 0 and ws <= 5
+        # (the fused level kernel keeps level 1 on chip at the shapes it takes, engine.level12_fused;
+        # otherwise the pyramid stores it and the estimate keeps it)
+        fused = not engine.level1_stored() and engine.level12_fused(h0, w0, ws)
         fit = max(1, budget // max(engine.tile_bytes(h0, w0, level1=not fused), 1))
         self.chunks = max(1, int(chunks or 1), -(-per // fit))
         g = self._gather()

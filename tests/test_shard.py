@@ -342,3 +342,27 @@ def test_band_solver_single_process_and_result_setting(monkeypatch):
             pass
     i1, i2 = shard.broadcast_pair(a, b, device='cpu')
     assert np.array_equal(i1.numpy(), a) and np.array_equal(i2.numpy(), b)
+
+
+@pytest.mark.parametrize('h0,w0', [(16, 192), (8, 512)])
+def test_band_solver_sizes_chunks_with_level1_where_it_is_stored(h0, w0, monkeypatch):
+    """Tiles the fused level kernel does not take (w0 not a power of two in 32 .. 256:
+    engine.level12_fused) store a float64 level 1, so BandSolver sizes its chunks with it:
+    tiles per chunk == budget // tile_bytes(level1=True).  A fused shape keeps the smaller
+    estimate."""
+    monkeypatch.delenv('DM_FUSE_L2', raising=False)
+    assert not engine.level1_stored() and not engine.level12_fused(h0, w0, 5)
+    T, ws = 12, 5
+    org = np.zeros((T, 2), dtype=np.int64)
+    img = np.zeros((h0 + ws - 1, w0 + ws - 1), dtype=np.uint8)
+    per = engine.tile_bytes(h0, w0, level1=True)
+    budget = 3 * per + per // 2
+    assert budget // engine.tile_bytes(h0, w0, level1=False) >= T   # the lean estimate: one chunk
+    band = shard.BandSolver(img, img, org, h0, w0, ws, 5, chunks=1, solver=_oracle_tiles, mem_budget=budget)
+    assert budget // per == 3
+    assert [len(idx) for idx in band.chunk_idx] == [budget // per] * (T // 3)
+    # a shape the fused kernel takes: level 1 is never stored, the estimate leaves it out
+    assert engine.level12_fused(16, 64, 5)
+    lean = engine.tile_bytes(16, 64, level1=False)
+    band = shard.BandSolver(img, img, org, 16, 64, ws, 5, chunks=1, solver=_oracle_tiles, mem_budget=3 * lean)
+    assert [len(idx) for idx in band.chunk_idx] == [3] * (T // 3)

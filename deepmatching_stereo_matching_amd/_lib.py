@@ -81,6 +81,8 @@ SIGNATURES = {
     'dm_fb_check': ([_P, _P, _I, _I, _I, ctypes.c_double, _P, _P, _P], ctypes.c_int),
     'dm_stitch_fb': ([_P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.c_double,
                       _P, _P, _P, _P], ctypes.c_int),
+    'dm_fill_bytes': ([_I, _I, _I], ctypes.c_size_t),
+    'dm_fill_holes': ([_P, _I, _I, _I, _I, _P, _P, _P, _P], ctypes.c_int),
 }
 
 _lib = None

@@ -636,3 +636,52 @@ def stitch(match, n, h0, w0, stride, modes, stream=None):
                                    len(mode_ids), L.ptr(dmap), L.ptr(score), L.stream_handle()),
                 'dm_stitch')
     return dmap, score
+
+
+def fill_iterations(fill):
+    """The ``fill=`` keyword of ImageCutSolver / shard.solve_image_sharded as a Jacobi step
+    count: an int in [0, 4096] (dm_fill_holes' range)."""
+    if isinstance(fill, bool) or not isinstance(fill, (int, np.integer)):
+        raise ValueError('fill must be an int (Jacobi iterations per level) or None')
+    if not 0 <= int(fill) <= 4096:
+        raise ValueError('fill iterations must be in [0, 4096] (got %r)' % (fill,))
+    return int(fill)
+
+
+def fill_holes(maps, iters=16, out=None, return_holes=False, stream=None):
+    """Dense maps from maps with holes (dm_fill_holes): cascadic push-pull with ``iters`` masked
+    Jacobi steps per level, deterministic, each map from its own holes.  ``maps``: a float64
+    device tensor [H][W] or [M][H][W]; a hole is a non-finite cell (NaN where dm_stitch found
+    no tile and where dm_stitch_fb's round trip missed).  Finite cells come out bit-identical;
+    the result is finite everywhere unless a whole map is a hole (it is then returned as it
+    is).  -> the filled tensor: ``out`` if given (``out=maps`` fills in place), else a new one;
+    with ``return_holes`` also the uint8 mask of the cells that were holes."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
+        raise ValueError('maps must be a float64 device (cuda) tensor')
+    if maps.dim() not in (2, 3):
+        raise ValueError('maps must be [H][W] or [M][H][W]')
+    iters = fill_iterations(iters)
+    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
+                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+    shape = tuple(maps.shape)
+    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    with _on(stream):
+        if out is not None and out.data_ptr() == maps.data_ptr():
+            src = out
+        else:
+            src = maps.contiguous()
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        if maps.numel() == 0:      # no cell, no hole
+            holes = torch.empty(shape, dtype=torch.uint8, device=maps.device)
+            return (out, holes) if return_holes else out
+        lib = L.load()
+        nbytes = lib.dm_fill_bytes(M, H, W)
+        if not nbytes:
+            raise NotImplementedError('fill_holes does not take %d maps of %d x %d cells' % (M, H, W))
+        work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+        holes = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_holes else None
+        L.check(lib.dm_fill_holes(L.ptr(src), M, H, W, int(iters), L.ptr(out), L.ptr(holes), L.ptr(work),
+                                  L.stream_handle()), 'dm_fill_holes')
+    return (out, holes) if return_holes else out

@@ -30,7 +30,8 @@ class ImageCutSolver():
         filtering_window_size=3,
         filtering_num=3,
         filtering_mode='average',
-        consistency=None
+        consistency=None,
+        fill=None
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -62,6 +63,9 @@ class ImageCutSolver():
         # forward-backward consistency tolerance in pixels (None: the reference's behaviour)
         self.consistency = consistency
         self.consistency_map = None
+        # Jacobi iterations of the hole fill of d_map (engine.fill_holes); None: d_map keeps its NaN
+        self.fill = engine.fill_iterations(fill) if fill is not None else None
+        self.hole_map = None
 
         self.log_flg = True
 
@@ -122,7 +126,9 @@ class ImageCutSolver():
         come back on every rank (one broadcast; tile_sharding(result='root'): rank 0 only, the
         others get None).  Every rank must then solve the same pair (shard.broadcast_pair
         sends it from rank 0).  With self.consistency set both branches solve the pair in both
-        directions and return a third tensor, the stitched round-trip error (engine.stitch_fb)."""
+        directions and return a third tensor, the stitched round-trip error (engine.stitch_fb).
+        With self.fill set d_map comes back filled (engine.fill_holes) and the uint8 mask of the
+        cells that were filled is the last tensor."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -140,12 +146,17 @@ class ImageCutSolver():
                                              self.sub_pix, self.filtering, self.filtering_window_size,
                                              self.filtering_num, self.filtering_mode,
                                              result=shard.shard_result(), grid=(n, origins),
-                                             consistency=self.consistency)
+                                             consistency=self.consistency, fill=self.fill)
         if self.consistency is not None:
             fwd, bwd = engine.solve_tiles_bidir(*args)
-            return engine.stitch_fb(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency)
-        match = engine.solve_tiles(*args)
-        return engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
+            maps = engine.stitch_fb(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency)
+        else:
+            match = engine.solve_tiles(*args)
+            maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
+        if self.fill is not None:
+            d, holes = engine.fill_holes(maps[0], self.fill, out=maps[0], return_holes=True)
+            maps = (d,) + tuple(maps[1:]) + (holes,)
+        return maps
 
     def _execute_matching(self):
         """
@@ -158,6 +169,8 @@ class ImageCutSolver():
         self.out_map = out_map.cpu().numpy() if out_map is not None else None
         if self.consistency is not None:   # [H][W] round-trip error; d_map is NaN where it exceeds the tolerance
             self.consistency_map = maps[2].cpu().numpy() if maps[2] is not None else None
+        if self.fill is not None:          # d_map is dense; hole_map marks the cells that were filled
+            self.hole_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
 
     def __call__(self):
         self._cut_and_pool()

@@ -382,7 +382,7 @@ def solve_tiles_sharded(img1, img2, origins, h0, w0, ws, method, sub_pix=True, f
 def solve_image_sharded(img1, img2, image_size, stride, window_size, method, modes=('elevation',),
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
                         filtering_mode='average', device=None, solver=None, stitcher=None,
-                        result='all', chunks=4, grid=None, consistency=None):
+                        result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -393,9 +393,15 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     so the bands, chunks and gathers are the one-direction ones over twice the tiles -- and rank
     0 splits the gathered tiles and stitches with the forward-backward check fused in
     (engine.stitch_fb, or ``stitcher(fwd, bwd, n, h0, w0, stride, modes, tol)``) ->
-    (d_map, out_map, err [H][W]) under the same ``result`` rules ((None, None, None) off root)."""
+    (d_map, out_map, err [H][W]) under the same ``result`` rules ((None, None, None) off root).
+    ``fill``: a count of Jacobi iterations; rank 0 then fills the holes of the stitched d_map
+    (the cells no tile covers and, with ``consistency``, the rejected ones) right after it
+    stitches (engine.fill_holes, or ``filler(d_map, iters) -> (filled, uint8 mask)``), and the
+    tuple gains the uint8 hole mask [len(modes)][H][W] as its LAST element, under the same
+    ``result`` rules.  out_map and err are never filled.  None: nothing changes."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
+    iters = engine.fill_iterations(fill) if fill is not None else None
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
     nmaps = 2
     if consistency is not None:
@@ -415,6 +421,14 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     else:
         stitch = stitcher or engine.stitch
         maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
+    if iters is not None:
+        nmaps += 1
+        if maps is not None:
+            if filler is not None:
+                d, holes = filler(maps[0], iters)
+            else:
+                d, holes = engine.fill_holes(maps[0], iters, out=maps[0], return_holes=True)
+            maps = (d,) + tuple(maps[1:]) + (holes,)
     if not _group() or world()[1] == 1:
         return maps
     if result == 'root':
@@ -424,7 +438,9 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     dev = band.device
     if maps is None:
         out = [torch.empty((len(modes), H, W), dtype=torch.float64, device=dev)]
-        out += [torch.empty((H, W), dtype=torch.float64, device=dev) for _ in range(nmaps - 1)]
+        out += [torch.empty((H, W), dtype=torch.float64, device=dev) for _ in range(2 if consistency is not None else 1)]
+        if iters is not None:
+            out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
     else:
         out = [torch.as_tensor(m) for m in maps]
     for t in out:

@@ -247,7 +247,40 @@ int dm_stitch_fb(const double *d_fwd, const double *d_bwd, int32_t n0, int32_t n
                  int32_t nmodes, double tol, double *d_dmap, double *d_score, double *d_err,
                  void *stream);
 
-/* ---- Gauss-Seidel post-processing (dm_postproc.hip) -------------
+/* ---- Hole fill (dm_fill.hip) -------------------------------------------------------------
+ * Not in the reference.  dm_stitch leaves NaN where no tile covers and dm_stitch_fb where the
+ * round trip misses, and one NaN poisons every cell the Gauss-Seidel sweeps below visit after
+ * it.  dm_fill_holes makes a map dense: cascadic push-pull with masked Jacobi relaxation,
+ * deterministic, each of the M maps of d_in [M][H][W] from its own holes.  A hole is a
+ * non-finite cell (NaN, +-inf; the range test is made on the double).  Level 0 is the map
+ * with (v, n) = (x, 1) at finite cells and (0, 0) at holes; level k + 1 has sides
+ * ceil(h / 2), ceil(w / 2).  In float64 without contraction, in the order written:
+ *   pull   s = ((n00 v00 + n01 v01) + n10 v10) + n11 v11;  m = ((n00 + n01) + n10) + n11
+ *          v' = m > 0 ? s / m : 0;  n' = m         (children outside the level: v = n = 0)
+ *   push   a cell with n == 0 takes (((9 a + 3 b) + 3 c) + d) * 0.0625 of the finished level
+ *          k + 1: a = p[I][J], b = p[I2][J], c = p[I][J2], d = p[I2][J2], I = i >> 1,
+ *          I2 = I + 1 for odd i and I - 1 for even i, clamped to the level (J likewise)
+ *   relax  `iters` Jacobi steps on the cells with n == 0: (((U + D) + L) + R) * 0.25, the
+ *          neighbours index-clamped, every read from the previous iterate
+ * Pull up to 1 x 1, then from the top down push and relax at EVERY level.  Finite cells come
+ * out bit-identical; the output is finite everywhere unless the whole map is a hole, and
+ * then it is the input bit for bit.  tests/test_fill_host.py restates this in numpy; the
+ * kernels equal it bit for bit. */
+
+/* Bytes of the workspace dm_fill_holes needs for M maps of H x W cells; 0 for a shape it does
+ * not take (a count below 1, H W > 2^31 - 1, M > 65535, a side above 64 * 65535). */
+size_t dm_fill_bytes(int32_t M, int32_t H, int32_t W);
+
+/* d_out [M][H][W] receives the filled maps and may equal d_in (in place).  d_holes
+ * ([M][H][W] uint8, may be NULL) receives 1 where the input cell was a hole, else 0.  d_work:
+ * dm_fill_bytes(M, H, W) bytes, 16-byte aligned, contents arbitrary.  0 <= iters <= 4096
+ * Jacobi steps per level.  DM_ERR_ARG for a null d_in / d_out / d_work, a count below 1 or
+ * iters out of range; DM_ERR_UNSUPPORTED for the other shapes dm_fill_bytes refuses.
+ * Validation precedes every HIP call. */
+int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t iters,
+                  double *d_out, uint8_t *d_holes, void *d_work, void *stream);
+
+/* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
  * float64 row-major h x w; `size` = (s0, s1) <= (h, w) bounds the sweeps as in the
@@ -327,8 +360,9 @@ const char *dm_last_error(void);
  * 4-tile column groups of dm_corr_stats' window operands at S = 128 / 256, 1.7 dm_seq_sum,
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
- * dm_pow14_variant).  dm_fb_check and dm_stitch_fb are additive entries within 1.10: no
- * existing entry, struct or workspace changed, so the version stays 110. */
+ * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes and dm_fill_holes are additive
+ * entries within 1.10: no existing entry, struct or workspace changed, so the version stays
+ * 110. */
 int dm_abi_version(void);
 
 #ifdef __cplusplus

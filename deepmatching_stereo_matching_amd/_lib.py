@@ -25,6 +25,10 @@ DM_TM_CCOEFF, DM_TM_CCOEFF_NORMED = 4, 5
 METHODS = {'cv2.TM_CCOEFF_NORMED': DM_TM_CCOEFF_NORMED, 'cv2.TM_CCOEFF': DM_TM_CCOEFF}
 CAL_MODES = {'elevation': 0, 'elevation2': 1, 'distance': 2}
 DM_GS_FWD4, DM_GS_BWD4, DM_GS_BILAT = 0, 1, 2
+DM_MERGE_LAST, DM_MERGE_CENTER, DM_MERGE_FEATHER, DM_MERGE_MEDIAN = 0, 1, 2, 3   # dm_stitch_merge rules
+MERGE_RULES = {'last': DM_MERGE_LAST, 'center': DM_MERGE_CENTER, 'feather': DM_MERGE_FEATHER,
+               'median': DM_MERGE_MEDIAN}
+DM_MERGE_MAX_CAND = 64   # tiles over one pixel that dm_stitch_merge takes
 
 
 class DmUnavailable(ImportError):
@@ -81,6 +85,8 @@ SIGNATURES = {
     'dm_fb_check': ([_P, _P, _I, _I, _I, ctypes.c_double, _P, _P, _P], ctypes.c_int),
     'dm_stitch_fb': ([_P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.c_double,
                       _P, _P, _P, _P], ctypes.c_int),
+    'dm_stitch_merge': ([_P, _P, _I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), _I, ctypes.c_double,
+                         _I, _I, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     'dm_fill_bytes': ([_I, _I, _I], ctypes.c_size_t),
     'dm_fill_holes': ([_P, _I, _I, _I, _I, _P, _P, _P, _P], ctypes.c_int),
 }

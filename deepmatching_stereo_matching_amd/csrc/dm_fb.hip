@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/dmstereo.h"
+#include "dm_fb_err.h"
 
 // error reporting lives in dm_kernels.hip (one thread-local message per thread)
 __attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
@@ -43,19 +44,6 @@ static int ffail(int code, const char *fmt, ...)
         hipError_t e_ = (x);                                                                 \
         if (e_ != hipSuccess) return ffail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
     } while (0)
-
-// round-trip error of cell l = i * w + j of one tile: f / b point at the tile's [3][h][w]
-// forward / backward maps, P = h * w.  The index into b is formed only from values the
-// floating-point range test has admitted: 0 <= qi < h, 0 <= qj < w.
-__device__ __forceinline__ double fb_err(const double *f, const double *b, size_t P, int h, int w, int i, int j,
-                                         size_t l)
-{
-    const double qi = floor(f[l] + 0.5), qj = floor(f[P + l] + 0.5);
-    if (!(qi >= 0.0 && qi < (double)h && qj >= 0.0 && qj < (double)w)) return NAN;
-    const size_t q = (size_t)(int)qi * w + (size_t)(int)qj;
-    const double dr = b[q] - (double)i, dc = b[P + q] - (double)j;
-    return sqrt(dr * dr + dc * dc);
-}
 
 // masked may be NULL or alias fwd: a thread reads its own forward cell before it writes it,
 // and no other thread reads that cell

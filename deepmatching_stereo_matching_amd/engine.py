@@ -623,6 +623,50 @@ def stitch_fb(fwd, bwd, n, h0, w0, stride, modes, tol, stream=None):
     return dmap, score, err
 
 
+def merge_rule(rule):
+    """The ``merge=`` keyword of ImageCutSolver / shard.solve_image_sharded as a dm_merge_rule."""
+    if rule not in L.MERGE_RULES:
+        raise ValueError('merge must be one of %s (got %r)' % (', '.join(sorted(L.MERGE_RULES)), rule))
+    return L.MERGE_RULES[rule]
+
+
+def stitch_merge(fwd, bwd, n, h0, w0, stride, modes, tol=None, rule='feather', min_count=1, stream=None):
+    """The stitch with every covering tile of a pixel merged instead of the last one kept
+    (dm_stitch_merge; include/dmstereo.h has the definition) -> (d_map, out_map, err or None,
+    spread, count).  ``rule``: 'last' (stitch / stitch_fb bit for bit), 'center' (the candidate
+    deepest inside its tile), 'feather' (edge-distance weighted mean) or 'median'.  ``bwd`` and
+    ``tol`` as in stitch_fb: a candidate whose round trip misses the tolerance is not merged;
+    ``bwd=None`` merges a one-direction solve (every finite candidate, err is None).  d_map is
+    NaN where fewer than ``min_count`` candidates are valid; spread [len(modes)][H][W] is max -
+    min of the valid candidates' values, count [H][W] (uint8) their number."""
+    mode_ids = [L.CAL_MODES[m] for m in modes]
+    rule_id = merge_rule(rule)
+    Hout, Wout = stride[0] * (n[0] - 1) + h0, stride[1] * (n[1] - 1) + w0
+    if bwd is None:
+        if tol is not None:
+            raise ValueError('a tolerance needs the backward tiles (bwd)')
+        f, b = _fb_pair(fwd, fwd)
+        b = None
+    else:
+        if tol is None:
+            raise ValueError('merging both directions needs a tolerance (tol)')
+        f, b = _fb_pair(fwd, bwd)
+    if tuple(f.shape) != (n[0] * n[1], 3, h0, w0):
+        raise ValueError('fwd / bwd must be [%d][3][%d][%d]' % (n[0] * n[1], h0, w0))
+    with _on(stream):
+        dmap = torch.empty((len(modes), Hout, Wout), dtype=torch.float64, device=f.device)
+        score = torch.empty((Hout, Wout), dtype=torch.float64, device=f.device)
+        err = torch.empty((Hout, Wout), dtype=torch.float64, device=f.device) if b is not None else None
+        spread = torch.empty((len(modes), Hout, Wout), dtype=torch.float64, device=f.device)
+        count = torch.empty((Hout, Wout), dtype=torch.uint8, device=f.device)
+        arr = (ctypes.c_int32 * max(1, len(mode_ids)))(*mode_ids)
+        L.check(L.load().dm_stitch_merge(L.ptr(f), L.ptr(b), n[0], n[1], h0, w0, stride[0], stride[1], arr,
+                                         len(mode_ids), float(tol) if b is not None else 0.0, rule_id,
+                                         int(min_count), L.ptr(dmap), L.ptr(score), L.ptr(err), L.ptr(spread),
+                                         L.ptr(count), L.stream_handle()), 'dm_stitch_merge')
+    return dmap, score, err, spread, count
+
+
 def stitch(match, n, h0, w0, stride, modes, stream=None):
     """ImageCutSolver._execute_matching stitching on the device -> (d_map, out_map)."""
     mode_ids = [L.CAL_MODES[m] for m in modes]

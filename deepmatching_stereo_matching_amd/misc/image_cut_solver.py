@@ -31,7 +31,9 @@ class ImageCutSolver():
         filtering_num=3,
         filtering_mode='average',
         consistency=None,
-        fill=None
+        fill=None,
+        merge=None,
+        merge_min_count=1
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -66,6 +68,13 @@ class ImageCutSolver():
         # Jacobi iterations of the hole fill of d_map (engine.fill_holes); None: d_map keeps its NaN
         self.fill = engine.fill_iterations(fill) if fill is not None else None
         self.hole_map = None
+        # rule that merges the overlapping tiles of a pixel (engine.stitch_merge); None: the last tile wins
+        if merge is not None:
+            engine.merge_rule(merge)
+        self.merge = merge
+        self.merge_min_count = merge_min_count
+        self.coverage_map = None
+        self.spread_map = None
 
         self.log_flg = True
 
@@ -128,7 +137,9 @@ class ImageCutSolver():
         sends it from rank 0).  With self.consistency set both branches solve the pair in both
         directions and return a third tensor, the stitched round-trip error (engine.stitch_fb).
         With self.fill set d_map comes back filled (engine.fill_holes) and the uint8 mask of the
-        cells that were filled is the last tensor."""
+        cells that were filled is the last tensor.  With self.merge set the stitch is
+        engine.stitch_merge (both directions when self.consistency is set) and the spread and the
+        uint8 count of valid candidates follow out_map / the error, before the hole mask."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -146,8 +157,17 @@ class ImageCutSolver():
                                              self.sub_pix, self.filtering, self.filtering_window_size,
                                              self.filtering_num, self.filtering_mode,
                                              result=shard.shard_result(), grid=(n, origins),
-                                             consistency=self.consistency, fill=self.fill)
-        if self.consistency is not None:
+                                             consistency=self.consistency, fill=self.fill,
+                                             merge=self.merge, merge_min_count=self.merge_min_count)
+        if self.merge is not None:
+            if self.consistency is not None:
+                fwd, bwd = engine.solve_tiles_bidir(*args)
+            else:
+                fwd, bwd = engine.solve_tiles(*args), None
+            maps = engine.stitch_merge(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency,
+                                       self.merge, self.merge_min_count)
+            maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
+        elif self.consistency is not None:
             fwd, bwd = engine.solve_tiles_bidir(*args)
             maps = engine.stitch_fb(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency)
         else:
@@ -169,6 +189,10 @@ class ImageCutSolver():
         self.out_map = out_map.cpu().numpy() if out_map is not None else None
         if self.consistency is not None:   # [H][W] round-trip error; d_map is NaN where it exceeds the tolerance
             self.consistency_map = maps[2].cpu().numpy() if maps[2] is not None else None
+        if self.merge is not None:         # valid candidates per pixel and their max - min, per mode
+            k = 3 if self.consistency is not None else 2
+            self.spread_map = maps[k].cpu().numpy() if maps[k] is not None else None
+            self.coverage_map = maps[k + 1].cpu().numpy() if maps[k + 1] is not None else None
         if self.fill is not None:          # d_map is dense; hole_map marks the cells that were filled
             self.hole_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
 

@@ -382,7 +382,8 @@ def solve_tiles_sharded(img1, img2, origins, h0, w0, ws, method, sub_pix=True, f
 def solve_image_sharded(img1, img2, image_size, stride, window_size, method, modes=('elevation',),
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
                         filtering_mode='average', device=None, solver=None, stitcher=None,
-                        result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None):
+                        result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
+                        merge=None, merge_min_count=1, merger=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -398,10 +399,18 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     (the cells no tile covers and, with ``consistency``, the rejected ones) right after it
     stitches (engine.fill_holes, or ``filler(d_map, iters) -> (filled, uint8 mask)``), and the
     tuple gains the uint8 hole mask [len(modes)][H][W] as its LAST element, under the same
-    ``result`` rules.  out_map and err are never filled.  None: nothing changes."""
+    ``result`` rules.  out_map and err are never filled.  None: nothing changes.
+    ``merge``: a rule name ('last', 'center', 'feather', 'median'); rank 0 then merges every
+    covering tile of a pixel instead of keeping the last (engine.stitch_merge with
+    ``merge_min_count``, both directions when ``consistency`` is set, or ``merger(fwd, bwd or
+    None, n, h0, w0, stride, modes, tol or None, rule, min_count) -> (d_map, out_map, err or None,
+    spread, count)``) and the tuple is (d_map, out_map[, err], spread [len(modes)][H][W], count
+    [H][W] uint8[, holes]); the hole mask stays last.  None: nothing changes."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     iters = engine.fill_iterations(fill) if fill is not None else None
+    if merge is not None:
+        engine.merge_rule(merge)
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
     nmaps = 2
     if consistency is not None:
@@ -413,8 +422,15 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                       chunks=chunks, dst=0, solver=solver)
     match = band.solve(sub_pix=sub_pix, filtering=filtering, filter_window_size=filter_window_size,
                        filtering_num=filtering_num, filtering_mode=filtering_mode)
+    if merge is not None:
+        nmaps += 2
     if match is None:
         maps = None
+    elif merge is not None:
+        fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
+        maps = (merger or engine.stitch_merge)(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes),
+                                               consistency, merge, merge_min_count)
+        maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
     elif consistency is not None:
         stitch = stitcher or engine.stitch_fb
         maps = stitch(match[:T], match[T:], n, image_size[0], image_size[1], stride, list(modes), consistency)
@@ -439,6 +455,9 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     if maps is None:
         out = [torch.empty((len(modes), H, W), dtype=torch.float64, device=dev)]
         out += [torch.empty((H, W), dtype=torch.float64, device=dev) for _ in range(2 if consistency is not None else 1)]
+        if merge is not None:
+            out.append(torch.empty((len(modes), H, W), dtype=torch.float64, device=dev))
+            out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
         if iters is not None:
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
     else:

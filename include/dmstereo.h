@@ -247,6 +247,60 @@ int dm_stitch_fb(const double *d_fwd, const double *d_bwd, int32_t n0, int32_t n
                  int32_t nmodes, double tol, double *d_dmap, double *d_score, double *d_err,
                  void *stream);
 
+/* ---- Overlap-merging stitch (dm_merge.hip) -------------------------------------------------
+ * Not in the reference.  dm_stitch and dm_stitch_fb keep the LAST tile that covers an output
+ * pixel; with overlapping tiles (stride S / 2: four solves per interior pixel) the other
+ * estimates are discarded.  dm_stitch_merge takes every covering tile as a candidate.  d_fwd
+ * and d_bwd (may be NULL: a one-direction solve) are dm_stitch_fb's.  All arithmetic is float64
+ * without contraction, in the order written.
+ *
+ * Candidates.  Output pixel (y, x) has as candidates every tile (i, j) with
+ * 0 <= y - i*stride0 < h0 and 0 <= x - j*stride1 < w0, enumerated with j as the outer loop and
+ * i as the inner loop, both ascending: the tile index t = j*n0 + i ascends, the order dm_stitch
+ * overwrites in.  For candidate c the local cell is (ly, lx) = (y - i*stride0, x - j*stride1);
+ *   r = F[t,0,ly,lx], q = F[t,1,ly,lx], s = F[t,2,ly,lx]
+ *   e_c     = err of the forward-backward check above at tile t, cell (ly, lx) when d_bwd is
+ *             given (indices are formed only from doubles that passed the range test)
+ *   valid_c = isfinite(r) && isfinite(q) && (d_bwd == NULL || e_c <= tol)
+ *   v_c,k   = dm_stitch's value of mode k: lx - q, ly - r, or sqrt(a*a + b*b) of a = ly - r,
+ *             b = lx - q
+ *   g_c     = min(ly + 1, h0 - ly) * min(lx + 1, w0 - lx)   (the distance to the tile's edge,
+ *             rows times columns: an exact integer, formed as a product of two doubles)
+ * m is the number of valid candidates.
+ *
+ * Rules.
+ *   DM_MERGE_LAST     bit for bit dm_stitch when d_bwd is NULL (the last candidate's values
+ *                     whatever they are) and dm_stitch_fb when it is given.  min_count must be 1.
+ *   DM_MERGE_CENTER   the valid candidate with the largest g, ties to the later candidate:
+ *                     value, score and err are that candidate's.
+ *   DM_MERGE_FEATHER  num = 0, den = 0; for each valid c in order num = num + g_c*v_c,
+ *                     den = den + g_c; the output is num / den.  The score likewise over s_c.
+ *   DM_MERGE_MEDIAN   rank(c) = #{c' valid : v' < v or (v' == v and c' < c)}.  Odd m: the value
+ *                     at rank (m-1)/2; even m: (a + b) * 0.5 of the values at ranks m/2 - 1 and
+ *                     m/2.  Per mode, and the score likewise over s_c.  (The value "at" a rank
+ *                     is that of the last candidate in order with that rank, NaN if none has it:
+ *                     the ranks are a permutation unless some s_c is NaN.)
+ * Rules 1 to 3: when m < min_count every dmap mode is NaN.  When m == 0 on a covered pixel the
+ * score and err are the last covering candidate's, as dm_stitch_fb leaves them; otherwise err
+ * is the minimum e_c over the valid candidates, except for CENTER (the chosen candidate's).
+ *
+ * Outputs, every rule: d_count [H][W] = m; d_spread [nmodes][H][W] = max - min of v_c,k over
+ * the valid candidates, NaN for m == 0.  A pixel no tile covers is NaN in every float output
+ * and 0 in d_count.  d_err, d_spread and d_count may be NULL.
+ *
+ * Validation precedes any HIP call and is dm_stitch_fb's, and: rule in 0..3; 1 <= min_count
+ * <= 255; a non-NULL d_err with a NULL d_bwd is DM_ERR_ARG; tol is checked only when d_bwd is
+ * given; min(n0, ceil(h0/stride0)) * min(n1, ceil(w0/stride1)) > DM_MERGE_MAX_CAND (more tiles
+ * over one pixel than the kernel's candidate mask holds) is DM_ERR_UNSUPPORTED. */
+enum dm_merge_rule { DM_MERGE_LAST = 0, DM_MERGE_CENTER = 1, DM_MERGE_FEATHER = 2, DM_MERGE_MEDIAN = 3 };
+#define DM_MERGE_MAX_CAND 64
+int dm_stitch_merge(const double *d_fwd, const double *d_bwd /* may be NULL */,
+                    int32_t n0, int32_t n1, int32_t h0, int32_t w0, int32_t stride0, int32_t stride1,
+                    const int32_t *modes, int32_t nmodes, double tol, int32_t rule, int32_t min_count,
+                    double *d_dmap, double *d_score, double *d_err /* may be NULL */,
+                    double *d_spread /* [nmodes][H][W], may be NULL */, uint8_t *d_count /* [H][W], may be NULL */,
+                    void *stream);
+
 /* ---- Hole fill (dm_fill.hip) -------------------------------------------------------------
  * Not in the reference.  dm_stitch leaves NaN where no tile covers and dm_stitch_fb where the
  * round trip misses, and one NaN poisons every cell the Gauss-Seidel sweeps below visit after
@@ -360,9 +414,9 @@ const char *dm_last_error(void);
  * 4-tile column groups of dm_corr_stats' window operands at S = 128 / 256, 1.7 dm_seq_sum,
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
- * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes and dm_fill_holes are additive
- * entries within 1.10: no existing entry, struct or workspace changed, so the version stays
- * 110. */
+ * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes and
+ * dm_stitch_merge are additive entries within 1.10: no existing entry, struct or workspace
+ * changed, so the version stays 110. */
 int dm_abi_version(void);
 
 #ifdef __cplusplus

@@ -89,6 +89,8 @@ SIGNATURES = {
                          _I, _I, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     'dm_fill_bytes': ([_I, _I, _I], ctypes.c_size_t),
     'dm_fill_holes': ([_P, _I, _I, _I, _I, _P, _P, _P, _P], ctypes.c_int),
+    'dm_speckle_bytes': ([_I, _I, _I], ctypes.c_size_t),
+    'dm_filter_speckles': ([_P, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P], ctypes.c_int),
 }
 
 _lib = None

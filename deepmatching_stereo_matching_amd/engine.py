@@ -729,3 +729,60 @@ def fill_holes(maps, iters=16, out=None, return_holes=False, stream=None):
         L.check(lib.dm_fill_holes(L.ptr(src), M, H, W, int(iters), L.ptr(out), L.ptr(holes), L.ptr(work),
                                   L.stream_handle()), 'dm_fill_holes')
     return (out, holes) if return_holes else out
+
+
+def speckle_params(speckle):
+    """The ``speckle=`` keyword of ImageCutSolver / shard.solve_image_sharded as (max_size,
+    max_diff): a pair of an int >= 0 (the largest segment removed, in cells) and a real >= 0
+    (the largest difference that joins two neighbours; inf allowed)."""
+    if isinstance(speckle, (str, bytes)) or not isinstance(speckle, (tuple, list)) or len(speckle) != 2:
+        raise ValueError('speckle must be a (max_size, max_diff) pair or None')
+    max_size, max_diff = speckle
+    if isinstance(max_size, bool) or not isinstance(max_size, (int, np.integer)) or not 0 <= int(max_size) < 2 ** 31:
+        raise ValueError('speckle max_size must be an int >= 0 (got %r)' % (max_size,))
+    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float, np.integer, np.floating)) \
+            or not float(max_diff) >= 0.0:
+        raise ValueError('speckle max_diff must be a real >= 0 (got %r)' % (max_diff,))
+    return int(max_size), float(max_diff)
+
+
+def filter_speckles(maps, max_size, max_diff, out=None, return_removed=False, return_sizes=False,
+                    return_labels=False, stream=None):
+    """Maps without their small segments (dm_filter_speckles), each map on its own.  ``maps``: a
+    float64 device tensor [H][W] or [M][H][W].  Two finite 4-neighbours are joined when they
+    differ by at most ``max_diff``; every cell of a connected segment of at most ``max_size``
+    cells becomes NaN, every other cell is copied bit for bit.  -> the filtered tensor: ``out``
+    if given (``out=maps`` filters in place), else a new one; then, as asked for, the uint8
+    mask of the cells removed, the size of each cell's segment (0 at holes; an int32 tensor,
+    sizes are at most 2^31 - 1) and its int32 label, the smallest linear index of the segment (-1 at holes)."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
+        raise ValueError('maps must be a float64 device (cuda) tensor')
+    if maps.dim() not in (2, 3):
+        raise ValueError('maps must be [H][W] or [M][H][W]')
+    max_size, max_diff = speckle_params((max_size, max_diff))
+    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
+                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+    shape = tuple(maps.shape)
+    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    with _on(stream):
+        if out is not None and out.data_ptr() == maps.data_ptr():
+            src = out
+        else:
+            src = maps.contiguous()
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        removed = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_removed else None
+        sizes = torch.empty(shape, dtype=torch.int32, device=maps.device) if return_sizes else None
+        labels = torch.empty(shape, dtype=torch.int32, device=maps.device) if return_labels else None
+        if maps.numel():      # (no cell, no segment)
+            lib = L.load()
+            nbytes = lib.dm_speckle_bytes(M, H, W)
+            if not nbytes:
+                raise NotImplementedError('filter_speckles does not take %d maps of %d x %d cells' % (M, H, W))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            L.check(lib.dm_filter_speckles(L.ptr(src), M, H, W, max_size, max_diff, L.ptr(out), L.ptr(removed),
+                                           L.ptr(sizes), L.ptr(labels), L.ptr(work), L.stream_handle()),
+                    'dm_filter_speckles')
+    res = (out,) + tuple(t for t in (removed, sizes, labels) if t is not None)
+    return res if len(res) > 1 else out

@@ -33,7 +33,8 @@ class ImageCutSolver():
         consistency=None,
         fill=None,
         merge=None,
-        merge_min_count=1
+        merge_min_count=1,
+        speckle=None
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -75,6 +76,10 @@ class ImageCutSolver():
         self.merge_min_count = merge_min_count
         self.coverage_map = None
         self.spread_map = None
+        # (max_size, max_diff) of the speckle filter of d_map (engine.filter_speckles), run after the
+        # stitch and before the fill; None: no segment is removed
+        self.speckle = engine.speckle_params(speckle) if speckle is not None else None
+        self.speckle_map = None
 
         self.log_flg = True
 
@@ -139,7 +144,10 @@ class ImageCutSolver():
         With self.fill set d_map comes back filled (engine.fill_holes) and the uint8 mask of the
         cells that were filled is the last tensor.  With self.merge set the stitch is
         engine.stitch_merge (both directions when self.consistency is set) and the spread and the
-        uint8 count of valid candidates follow out_map / the error, before the hole mask."""
+        uint8 count of valid candidates follow out_map / the error, before the hole mask.  With
+        self.speckle set d_map loses its small segments (engine.filter_speckles) after the stitch
+        and before the fill, and the uint8 mask of the cells removed comes immediately before the
+        hole mask: (d_map, out_map[, err][, spread, count][, speckles][, holes])."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -158,7 +166,8 @@ class ImageCutSolver():
                                              self.filtering_num, self.filtering_mode,
                                              result=shard.shard_result(), grid=(n, origins),
                                              consistency=self.consistency, fill=self.fill,
-                                             merge=self.merge, merge_min_count=self.merge_min_count)
+                                             merge=self.merge, merge_min_count=self.merge_min_count,
+                                             speckle=self.speckle)
         if self.merge is not None:
             if self.consistency is not None:
                 fwd, bwd = engine.solve_tiles_bidir(*args)
@@ -173,6 +182,9 @@ class ImageCutSolver():
         else:
             match = engine.solve_tiles(*args)
             maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
+        if self.speckle is not None:
+            d, removed = engine.filter_speckles(maps[0], *self.speckle, out=maps[0], return_removed=True)
+            maps = (d,) + tuple(maps[1:]) + (removed,)
         if self.fill is not None:
             d, holes = engine.fill_holes(maps[0], self.fill, out=maps[0], return_holes=True)
             maps = (d,) + tuple(maps[1:]) + (holes,)
@@ -193,6 +205,9 @@ class ImageCutSolver():
             k = 3 if self.consistency is not None else 2
             self.spread_map = maps[k].cpu().numpy() if maps[k] is not None else None
             self.coverage_map = maps[k + 1].cpu().numpy() if maps[k + 1] is not None else None
+        if self.speckle is not None:       # the cells the speckle filter removed (before any fill)
+            k = -2 if self.fill is not None else -1
+            self.speckle_map = maps[k].cpu().numpy().astype(bool) if maps[k] is not None else None
         if self.fill is not None:          # d_map is dense; hole_map marks the cells that were filled
             self.hole_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
 

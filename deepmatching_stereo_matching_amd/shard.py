@@ -383,7 +383,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
                         filtering_mode='average', device=None, solver=None, stitcher=None,
                         result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
-                        merge=None, merge_min_count=1, merger=None):
+                        merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -405,10 +405,17 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     ``merge_min_count``, both directions when ``consistency`` is set, or ``merger(fwd, bwd or
     None, n, h0, w0, stride, modes, tol or None, rule, min_count) -> (d_map, out_map, err or None,
     spread, count)``) and the tuple is (d_map, out_map[, err], spread [len(modes)][H][W], count
-    [H][W] uint8[, holes]); the hole mask stays last.  None: nothing changes."""
+    [H][W] uint8[, holes]); the hole mask stays last.  None: nothing changes.
+    ``speckle``: a (max_size, max_diff) pair; rank 0 then removes the small segments of the
+    stitched d_map after the stitch and before the fill (engine.filter_speckles, or
+    ``speckler(d_map, max_size, max_diff) -> (filtered, uint8 mask)``), so the removed cells are
+    filled like any other hole, and the tuple gains the uint8 mask [len(modes)][H][W] of the
+    cells removed immediately before the hole mask: (d_map, out_map[, err][, spread, count]
+    [, speckles][, holes]).  None: nothing changes."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     iters = engine.fill_iterations(fill) if fill is not None else None
+    spk = engine.speckle_params(speckle) if speckle is not None else None
     if merge is not None:
         engine.merge_rule(merge)
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
@@ -437,6 +444,14 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     else:
         stitch = stitcher or engine.stitch
         maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
+    if spk is not None:
+        nmaps += 1
+        if maps is not None:
+            if speckler is not None:
+                d, removed = speckler(maps[0], spk[0], spk[1])
+            else:
+                d, removed = engine.filter_speckles(maps[0], spk[0], spk[1], out=maps[0], return_removed=True)
+            maps = (d,) + tuple(maps[1:]) + (removed,)
     if iters is not None:
         nmaps += 1
         if maps is not None:
@@ -458,6 +473,8 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
         if merge is not None:
             out.append(torch.empty((len(modes), H, W), dtype=torch.float64, device=dev))
             out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
+        if spk is not None:
+            out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
         if iters is not None:
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
     else:

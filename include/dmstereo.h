@@ -334,6 +334,39 @@ size_t dm_fill_bytes(int32_t M, int32_t H, int32_t W);
 int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t iters,
                   double *d_out, uint8_t *d_holes, void *d_work, void *stream);
 
+/* ---- Speckle filter (dm_speckle.hip) -----------------------------------------------------
+ * Not in the reference.  The round-trip check keeps a mismatch when both directions agree on
+ * the wrong place, and the fill and the sweeps below then smear that blob into its neighbours.
+ * dm_filter_speckles removes small isolated segments of a map, as OpenCV's filterSpeckles
+ * does, each of the M maps of d_in [M][H][W] on its own:
+ *   finite   a cell that passes the range test made on the double; NaN and +-inf are holes
+ *   joined   two finite 4-neighbours a, b with fabs(a - b) <= max_diff, in float64 without
+ *            contraction (a difference that overflows to inf is joined only by max_diff = +inf)
+ *   segment  a connected component of the join graph; its size is its cell count, its label
+ *            the smallest linear index i W + j among its cells
+ * Every cell of a segment with size <= max_size becomes NaN in d_out (the quiet NaN dm_stitch
+ * writes); every other cell, input holes included, is copied bit for bit.  max_size = 0
+ * removes nothing and still reports sizes and labels.  Labels and sizes are integers and do
+ * not depend on the schedule: the outputs are bit-identical from run to run.
+ * tests/test_speckle_host.py restates this in plain loops; the kernels equal it bit for bit. */
+
+/* Bytes of the workspace dm_filter_speckles needs for M maps of H x W cells; 0 for a shape it
+ * does not take (a count below 1, H W > 2^31 - 1: labels are int32, M > 65535, a side above
+ * 64 * 65535). */
+size_t dm_speckle_bytes(int32_t M, int32_t H, int32_t W);
+
+/* d_out [M][H][W] may equal d_in (in place).  Optional outputs, each [M][H][W] and may be
+ * NULL: d_removed (uint8) 1 where this call removed the cell, else 0 (input holes: 0); d_size
+ * (uint32) the size of the cell's segment as found, 0 at input holes; d_label (int32) its
+ * label, -1 at input holes.  d_work: dm_speckle_bytes(M, H, W) bytes, 16-byte aligned,
+ * contents arbitrary.  DM_ERR_ARG for a null d_in / d_out / d_work, a count below 1,
+ * max_size < 0, a negative or NaN max_diff (+inf is allowed); DM_ERR_UNSUPPORTED for the other
+ * shapes dm_speckle_bytes refuses.  Validation precedes every HIP call; nothing is allocated,
+ * nothing synchronises, all work goes on `stream`. */
+int dm_filter_speckles(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t max_size,
+                       double max_diff, double *d_out, uint8_t *d_removed, uint32_t *d_size,
+                       int32_t *d_label, void *d_work, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -414,8 +447,8 @@ const char *dm_last_error(void);
  * 4-tile column groups of dm_corr_stats' window operands at S = 128 / 256, 1.7 dm_seq_sum,
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
- * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes and
- * dm_stitch_merge are additive entries within 1.10: no existing entry, struct or workspace
+ * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
+ * dm_stitch_merge, dm_speckle_bytes and dm_filter_speckles are additive entries within 1.10: no existing entry, struct or workspace
  * changed, so the version stays 110. */
 int dm_abi_version(void);
 

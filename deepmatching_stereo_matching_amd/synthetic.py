@@ -59,3 +59,61 @@ def stereo_pair(h, w, seed=0, dx=2, max_disp=None, sinusoidal=False):
                                       np.cos(2 * np.pi * yy / max(h, 1)))).astype(np.int64)
         img2 = tex[4 + yy, 4 + xx + d].astype(np.uint8)
     return img1, img2
+
+
+CONTENT_KINDS = ('binary', 'identical', 'dark', 'bright', 'dark_bright', 'low4', 'high4',
+                 'checker', 'stripes', 'edge', 'const')
+
+
+def content_pair(kind, h, w, seed):
+    """Return (img1, img2), uint8 (h, w), of one content class of CONTENT_KINDS: images at the
+    ends of the value range, with exact ties, or flat -- what the smooth texture of stereo_pair
+    never is ("Value ranges").  Unless noted below, a field of w + 3
+    columns is generated and img1 = field[:, :w], img2 = field[:, 3:] (a shift of 3 columns).
+
+      binary       i.i.d. pixels in {0, 255}
+      identical    binary, img2 == img1 (r = 1 exactly at q = p)
+      dark         0, and 255 with probability 0.02: flat patches next to textured ones at
+                   ws = 5, and still an all-zero 15 x 15 patch in a tile (the lowest sums)
+      bright       255 - dark
+      dark_bright  dark against 255 - its shifted self (the most negative products)
+      low4         i.i.d. pixels in {0 .. 3}
+      high4        252 + low4 (tiny variances under the largest sums)
+      checker      255 * ((x // 2 + y // 2) % 2), img2 shifted by 1 column (every row of
+                   level 0 has many exact maxima)
+      stripes      10 where x % 8 < 4, else 240
+      edge         0 left of column w // 2 of the field, 255 from there on
+      const        img1 all 255, img2 all 0 (every patch and every window flat)"""
+    if kind not in CONTENT_KINDS:
+        raise ValueError('unknown content kind %r' % (kind,))
+    rng = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:h, 0:w + 3]
+    if kind in ('binary', 'identical'):
+        f = 255 * rng.integers(0, 2, size=(h, w + 3))
+    elif kind in ('dark', 'bright', 'dark_bright'):
+        f = 255 * (rng.random((h, w + 3)) < 0.02)
+        if kind == 'bright':
+            f = 255 - f
+    elif kind in ('low4', 'high4'):
+        f = rng.integers(0, 4, size=(h, w + 3)) + (252 if kind == 'high4' else 0)
+    elif kind == 'checker':
+        f = 255 * ((xx // 2 + yy // 2) % 2)
+    elif kind == 'stripes':
+        f = np.where(xx % 8 < 4, 10, 240)
+    elif kind == 'edge':
+        f = np.where(xx < w // 2, 0, 255)
+    else:
+        f = np.full((h, w + 3), 255)
+    f = f.astype(np.uint8)
+    img1 = f[:, :w].copy()
+    if kind == 'identical':
+        img2 = img1.copy()
+    elif kind == 'dark_bright':
+        img2 = 255 - f[:, 3:]
+    elif kind == 'checker':
+        img2 = f[:, 1:w + 1].copy()
+    elif kind == 'const':
+        img2 = np.zeros((h, w), dtype=np.uint8)
+    else:
+        img2 = f[:, 3:].copy()
+    return img1, img2

@@ -29,6 +29,7 @@ DM_MERGE_LAST, DM_MERGE_CENTER, DM_MERGE_FEATHER, DM_MERGE_MEDIAN = 0, 1, 2, 3  
 MERGE_RULES = {'last': DM_MERGE_LAST, 'center': DM_MERGE_CENTER, 'feather': DM_MERGE_FEATHER,
                'median': DM_MERGE_MEDIAN}
 DM_MERGE_MAX_CAND = 64   # tiles over one pixel that dm_stitch_merge takes
+DM_BILAT_FILL, DM_BILAT_GUIDE_U8 = 1, 2   # dm_bilateral_filter flags
 
 
 class DmUnavailable(ImportError):
@@ -91,6 +92,9 @@ SIGNATURES = {
     'dm_fill_holes': ([_P, _I, _I, _I, _I, _P, _P, _P, _P], ctypes.c_int),
     'dm_speckle_bytes': ([_I, _I, _I], ctypes.c_size_t),
     'dm_filter_speckles': ([_P, _I, _I, _I, _I, ctypes.c_double, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    'dm_bilateral_bytes': ([_I, _I, _I], ctypes.c_size_t),
+    'dm_bilateral_filter': ([_P, _P, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _I, _I, _P, _P, _P, _P],
+                            ctypes.c_int),
 }
 
 _lib = None

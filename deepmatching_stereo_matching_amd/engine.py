@@ -786,3 +786,97 @@ def filter_speckles(maps, max_size, max_diff, out=None, return_removed=False, re
                     'dm_filter_speckles')
     res = (out,) + tuple(t for t in (removed, sizes, labels) if t is not None)
     return res if len(res) > 1 else out
+
+
+def smooth_params(smooth):
+    """The ``smooth=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius,
+    sigma_color, sigma_space): an int in [1, 15] (the window is (2 radius + 1)^2 taps) and two
+    reals > 0 (inf allowed: a flat weight)."""
+    if isinstance(smooth, (str, bytes)) or not isinstance(smooth, (tuple, list)) or len(smooth) != 3:
+        raise ValueError('smooth must be a (radius, sigma_color, sigma_space) triple or None')
+    radius, sigma_color, sigma_space = smooth
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 15:
+        raise ValueError('smooth radius must be an int in [1, 15] (got %r)' % (radius,))
+    for name, s in (('sigma_color', sigma_color), ('sigma_space', sigma_space)):
+        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not float(s) > 0.0:
+            raise ValueError('smooth %s must be a real > 0 (got %r)' % (name, s))
+    return int(radius), float(sigma_color), float(sigma_space)
+
+
+def bilateral_filter(maps, radius, sigma_color, sigma_space, guide=None, iters=1, fill=False, out=None,
+                     return_filled=False, stream=None):
+    """Edge-preserving smoothing of maps with holes (dm_bilateral_filter), each map on its own.
+    ``maps``: a float64 device tensor [H][W] or [M][H][W].  A cell becomes the mean of the finite
+    cells of its (2 radius + 1)^2 window, weighted by exp(-d^2 / (2 sigma_space^2)) of their
+    distance and exp(-c^2 / (2 sigma_color^2)) of the difference of the guide; ``guide``: None
+    (the map guides itself) or a float64 or uint8 device tensor [H][W] (shared by all maps) or of
+    ``maps``' shape; cells where the map or the guide is not finite are left out.  ``iters``
+    passes in [1, 64].  Holes (NaN, +-inf) stay bit-identical unless ``fill`` is set (it needs a
+    guide): a hole is then filled from the usable cells of its window, if any.  -> the smoothed
+    tensor: ``out`` if given (``out=maps`` smooths in place), else a new one; with
+    ``return_filled`` also the uint8 mask of the holes that came out finite."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
+        raise ValueError('maps must be a float64 device (cuda) tensor')
+    if maps.dim() not in (2, 3):
+        raise ValueError('maps must be [H][W] or [M][H][W]')
+    radius, sigma_color, sigma_space = smooth_params((radius, sigma_color, sigma_space))
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= 64:
+        raise ValueError('iters must be an int in [1, 64] (got %r)' % (iters,))
+    shape = tuple(maps.shape)
+    flags = 0
+    if guide is not None:
+        if not (isinstance(guide, torch.Tensor) and guide.device == maps.device and
+                guide.dtype in (torch.float64, torch.uint8)):
+            raise ValueError('guide must be a float64 or uint8 tensor on maps\' device')
+        if tuple(guide.shape) not in (shape, shape[-2:]):
+            raise ValueError('guide must be [H][W] or of maps\' shape')
+        if guide.dtype == torch.uint8:
+            flags |= L.DM_BILAT_GUIDE_U8
+    if fill:
+        if guide is None:
+            raise ValueError('fill needs a guide')
+        flags |= L.DM_BILAT_FILL
+    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
+                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    with _on(stream):
+        if out is not None and out.data_ptr() == maps.data_ptr():
+            src = out
+        else:
+            src = maps.contiguous()
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        filled = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_filled else None
+        if maps.numel():      # (no cell, nothing to smooth)
+            lib = L.load()
+            nbytes = lib.dm_bilateral_bytes(M, H, W)
+            if not nbytes:
+                raise NotImplementedError('bilateral_filter does not take %d maps of %d x %d cells' % (M, H, W))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            g = guide.contiguous() if guide is not None else None
+            gmaps = M if g is not None and g.dim() == 3 else 1
+            L.check(lib.dm_bilateral_filter(L.ptr(src), L.ptr(g), gmaps, M, H, W, radius, bilateral_den(sigma_color),
+                                            bilateral_den(sigma_space), int(iters), flags, L.ptr(out),
+                                            L.ptr(filled), L.ptr(work), L.stream_handle()), 'dm_bilateral_filter')
+    return (out, filled) if return_filled else out
+
+
+def smooth_guide(img1, exclusive_pix, d_map):
+    """The 'image' guide of ``smooth=``: img1[e:e + H, e:e + W] as a uint8 tensor on d_map's
+    device, [H][W] d_map's last two sides -- map cell (y, x) is the patch centred at
+    (y + e, x + e) of the image."""
+    H, W = d_map.shape[-2:]
+    e = int(exclusive_pix)
+    if np.shape(img1)[0] < e + H or np.shape(img1)[1] < e + W:
+        raise ValueError('image %r does not cover the %d x %d map' % (tuple(np.shape(img1)), H, W))
+    return to_device_u8(img1, d_map.device)[e:e + H, e:e + W].contiguous()
+
+
+def bilateral_den(sigma):
+    """den_color / den_space of dm_bilateral_filter: 2.0 * sigma**2 as Python evaluates it
+    (dm_make_weight's convention); a square beyond the float64 range is inf."""
+    try:
+        return 2.0 * float(sigma) ** 2
+    except OverflowError:
+        return float('inf')

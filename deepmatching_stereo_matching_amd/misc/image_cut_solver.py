@@ -34,7 +34,9 @@ class ImageCutSolver():
         fill=None,
         merge=None,
         merge_min_count=1,
-        speckle=None
+        speckle=None,
+        smooth=None,
+        smooth_guide='image'
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -80,6 +82,13 @@ class ImageCutSolver():
         # stitch and before the fill; None: no segment is removed
         self.speckle = engine.speckle_params(speckle) if speckle is not None else None
         self.speckle_map = None
+        # (radius, sigma_color, sigma_space) of the bilateral smoothing of d_map (engine.bilateral_filter),
+        # run last: after the stitch, the speckle filter and the fill; None: d_map is not smoothed.
+        # smooth_guide: 'image' (img1 under the map's cells, uint8) or 'self' (the map guides itself)
+        self.smooth = engine.smooth_params(smooth) if smooth is not None else None
+        if smooth_guide not in ('image', 'self'):
+            raise ValueError("smooth_guide must be 'image' or 'self'")
+        self.smooth_guide = smooth_guide
 
         self.log_flg = True
 
@@ -147,7 +156,9 @@ class ImageCutSolver():
         uint8 count of valid candidates follow out_map / the error, before the hole mask.  With
         self.speckle set d_map loses its small segments (engine.filter_speckles) after the stitch
         and before the fill, and the uint8 mask of the cells removed comes immediately before the
-        hole mask: (d_map, out_map[, err][, spread, count][, speckles][, holes])."""
+        hole mask: (d_map, out_map[, err][, spread, count][, speckles][, holes]).  With self.smooth
+        set d_map is smoothed last (engine.bilateral_filter, all modes in one call; holes stay
+        holes, self.fill is what fills); no tensor is added."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -167,7 +178,8 @@ class ImageCutSolver():
                                              result=shard.shard_result(), grid=(n, origins),
                                              consistency=self.consistency, fill=self.fill,
                                              merge=self.merge, merge_min_count=self.merge_min_count,
-                                             speckle=self.speckle)
+                                             speckle=self.speckle, smooth=self.smooth,
+                                             smooth_guide=self.smooth_guide)
         if self.merge is not None:
             if self.consistency is not None:
                 fwd, bwd = engine.solve_tiles_bidir(*args)
@@ -188,6 +200,10 @@ class ImageCutSolver():
         if self.fill is not None:
             d, holes = engine.fill_holes(maps[0], self.fill, out=maps[0], return_holes=True)
             maps = (d,) + tuple(maps[1:]) + (holes,)
+        if self.smooth is not None:
+            guide = engine.smooth_guide(self.img1, self.exclusive_pix, maps[0]) if self.smooth_guide == 'image' else None
+            d = engine.bilateral_filter(maps[0], *self.smooth, guide=guide, out=maps[0])
+            maps = (d,) + tuple(maps[1:])
         return maps
 
     def _execute_matching(self):

@@ -383,7 +383,8 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
                         filtering_mode='average', device=None, solver=None, stitcher=None,
                         result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
-                        merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None):
+                        merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
+                        smooth=None, smooth_guide='image', smoother=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -411,11 +412,20 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     ``speckler(d_map, max_size, max_diff) -> (filtered, uint8 mask)``), so the removed cells are
     filled like any other hole, and the tuple gains the uint8 mask [len(modes)][H][W] of the
     cells removed immediately before the hole mask: (d_map, out_map[, err][, spread, count]
-    [, speckles][, holes]).  None: nothing changes."""
+    [, speckles][, holes]).  None: nothing changes.
+    ``smooth``: a (radius, sigma_color, sigma_space) triple; rank 0 then smooths d_map last, after
+    the fill, all modes in one call (engine.bilateral_filter, or ``smoother(d_map, guide or None,
+    radius, sigma_color, sigma_space) -> d_map``).  ``smooth_guide``: 'image' -- the guide is
+    img1[e:e + H, e:e + W] as uint8, e = (window_size - 1) // 2, the pixel under each map cell
+    -- or 'self'.  Holes stay holes; no tensor is added.  None: nothing changes."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     iters = engine.fill_iterations(fill) if fill is not None else None
     spk = engine.speckle_params(speckle) if speckle is not None else None
+    smo = engine.smooth_params(smooth) if smooth is not None else None
+    if smooth_guide not in ('image', 'self'):
+        raise ValueError("smooth_guide must be 'image' or 'self'")
+    guide_img = img1      # (consistency stacks the pair below)
     if merge is not None:
         engine.merge_rule(merge)
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
@@ -460,6 +470,16 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             else:
                 d, holes = engine.fill_holes(maps[0], iters, out=maps[0], return_holes=True)
             maps = (d,) + tuple(maps[1:]) + (holes,)
+    if smo is not None and maps is not None:
+        e = (window_size - 1) // 2
+        if smoother is not None:
+            Hm, Wm = np.shape(maps[0])[-2:]
+            guide = np.asarray(guide_img)[e:e + Hm, e:e + Wm] if smooth_guide == 'image' else None
+            d = smoother(maps[0], guide, *smo)
+        else:
+            guide = engine.smooth_guide(guide_img, e, maps[0]) if smooth_guide == 'image' else None
+            d = engine.bilateral_filter(maps[0], *smo, guide=guide, out=maps[0])
+        maps = (d,) + tuple(maps[1:])
     if not _group() or world()[1] == 1:
         return maps
     if result == 'root':

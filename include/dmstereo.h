@@ -367,6 +367,57 @@ int dm_filter_speckles(const double *d_in, int32_t M, int32_t H, int32_t W, int3
                        double max_diff, double *d_out, uint8_t *d_removed, uint32_t *d_size,
                        int32_t *d_label, void *d_work, void *stream);
 
+/* ---- Joint bilateral filter (dm_bilateral.hip) -------------------------------------------
+ * The live branch of the reference's optimize_looper.py (:76-77) is cv2.bilateralFilter on a
+ * uint8 cast of the map.  dm_bilateral_filter is its float64, NaN-aware, guided form: it
+ * smooths each of the M maps of d_in [M][H][W] on its own.  All arithmetic is float64 without
+ * contraction, in the order written; exp is the pinned dm_exp (csrc/dm_exp.h).  One pass, with
+ * input X and guide G:
+ *   guide    d_guide NULL: the map guides itself, G is X (in a later pass that pass's input).
+ *            Otherwise G is d_guide, [H][W] shared by all maps (guide_maps == 1) or [M][H][W]
+ *            (guide_maps == M), float64, or uint8 with DM_BILAT_GUIDE_U8 (value (double)g);
+ *            an external guide is the same in every pass.
+ *   usable   a tap inside the map at which X and G are both finite (range test on the double;
+ *            NaN and +-inf in the map are holes, as in dm_fill_holes)
+ *   cell     G[i, j] not finite: the output is X[i, j] bit for bit.  X[i, j] a hole and
+ *            DM_BILAT_FILL not set: likewise.  Otherwise num = 0, den = 0 and, dy = -r .. r
+ *            outer, dx = -r .. r inner, both ascending, for each usable tap (i + dy, j + dx):
+ *              c  = G[i, j] - G[tap];  wc = dm_exp(-(c * c) / den_color)
+ *              ws = dm_exp(-(double)(dy*dy + dx*dx) / den_space)
+ *              w  = ws * wc;  a tap with !(w > 0) is skipped
+ *              num = num + w * X[tap];  den = den + w
+ *            The output is num / den when den > 0, else X[i, j] bit for bit.  A finite centre
+ *            has den >= 1: its own tap weighs exactly 1.
+ *   FILL     DM_BILAT_FILL (needs an external guide): a hole whose window holds a usable tap
+ *            is filled from those taps.
+ * `iters` passes, pass k + 1 reading pass k's output.  It follows that without FILL a hole
+ * stays bit-identical, that a map that is all holes comes out as it went in, that a finite
+ * cell comes out finite as long as no w * X overflows, and that the outputs are bit-identical
+ * from run to run (a thread sums its cell's window sequentially; no atomics).
+ * den_color, den_space: 2.0 * sigma**2 as the caller's Python evaluates it (dm_make_weight's
+ * convention); both > 0, +inf allowed (a flat weight).
+ * tests/test_bilateral_host.py restates this in plain loops; the kernel equals it bit for
+ * bit, and its uint8-guide path (a 256-entry table of wc) equals its float64-guide path. */
+enum { DM_BILAT_FILL = 1, DM_BILAT_GUIDE_U8 = 2 };
+
+/* Bytes of the workspace dm_bilateral_filter needs for M maps of H x W cells; 0 for a shape it
+ * does not take (dm_fill_bytes' limits: a count below 1, H W > 2^31 - 1, M > 65535, a side
+ * above 64 * 65535). */
+size_t dm_bilateral_bytes(int32_t M, int32_t H, int32_t W);
+
+/* d_out [M][H][W] may equal d_in (in place).  d_filled ([M][H][W] uint8, may be NULL) receives
+ * 1 where d_in was a hole and d_out is finite, else 0.  d_work: dm_bilateral_bytes(M, H, W)
+ * bytes, 16-byte aligned, contents arbitrary.  1 <= radius <= 15, 1 <= iters <= 64.
+ * DM_ERR_ARG for a null d_in / d_out / d_work, a count below 1, radius or iters out of range,
+ * a den_* that is not > 0 (NaN included), unknown flag bits, guide_maps not 1 or M when a
+ * guide is given, DM_BILAT_FILL or DM_BILAT_GUIDE_U8 without a guide; DM_ERR_UNSUPPORTED for
+ * the other shapes dm_bilateral_bytes refuses.  Validation precedes every HIP call; nothing is
+ * allocated, nothing synchronises, all work goes on `stream`. */
+int dm_bilateral_filter(const double *d_in, const void *d_guide /* may be NULL */, int32_t guide_maps,
+                        int32_t M, int32_t H, int32_t W, int32_t radius, double den_color, double den_space,
+                        int32_t iters, int32_t flags, double *d_out, uint8_t *d_filled /* may be NULL */,
+                        void *d_work, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -448,7 +499,8 @@ const char *dm_last_error(void);
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
- * dm_stitch_merge, dm_speckle_bytes and dm_filter_speckles are additive entries within 1.10: no existing entry, struct or workspace
+ * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes and
+ * dm_bilateral_filter are additive entries within 1.10: no existing entry, struct or workspace
  * changed, so the version stays 110. */
 int dm_abi_version(void);
 

@@ -880,3 +880,88 @@ def bilateral_den(sigma):
         return 2.0 * float(sigma) ** 2
     except OverflowError:
         return float('inf')
+
+
+def median_params(median):
+    """The ``median=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius, iters):
+    an int radius in [1, 7] (the window is (2 radius + 1)^2 taps), ``(radius,)`` or ``(radius,
+    iters)`` with iters, the number of passes, an int in [1, 64] (default 1)."""
+    if isinstance(median, (tuple, list)):
+        if not 1 <= len(median) <= 2:
+            raise ValueError('median must be a radius, (radius,), (radius, iters) or None')
+        radius, iters = median[0], (median[1] if len(median) == 2 else 1)
+    else:
+        radius, iters = median, 1
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
+        raise ValueError('median radius must be an int in [1, 7] (got %r)' % (radius,))
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= 64:
+        raise ValueError('median iters must be an int in [1, 64] (got %r)' % (iters,))
+    return int(radius), int(iters)
+
+
+def median_filter(maps, radius, weight=None, iters=1, min_count=1, fill=False, out=None, return_changed=False,
+                  stream=None):
+    """Impulse filter of maps with holes (dm_median_filter), each map on its own.  ``maps``: a
+    float64 device tensor [H][W] or [M][H][W], or a numpy array of such a shape (it is copied to
+    the default device).  A cell becomes the lower median, by the order-preserving key of the
+    double, of the finite cells of its (2 radius + 1)^2 window; with ``weight`` -- a float64
+    tensor (or array) [H][W], shared by all maps, or of ``maps``' shape -- the weighted lower
+    median: the smallest window value at which the weights of the values up to it, summed in
+    window order, reach half their total; taps whose weight is not in (0, inf) are left out.
+    ``iters`` passes in [1, 64].  A cell with fewer than ``min_count`` usable taps is copied.
+    Holes (NaN, +-inf) stay bit-identical unless ``fill`` is set: a hole then receives the median
+    of its window.  Every finite output is one of the window's own values, bit for bit.  -> the
+    filtered tensor: ``out`` if given (``out=maps`` filters in place), else a new one; with
+    ``return_changed`` also the uint8 mask of the cells whose bits changed."""
+    if isinstance(maps, np.ndarray):
+        if maps.dtype != np.float64:
+            raise ValueError('maps must be float64')
+        maps = torch.from_numpy(np.ascontiguousarray(maps)).to(default_device())
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
+        raise ValueError('maps must be a float64 device (cuda) tensor or a float64 numpy array')
+    if maps.dim() not in (2, 3):
+        raise ValueError('maps must be [H][W] or [M][H][W]')
+    radius, iters = median_params((radius, iters))
+    K = (2 * radius + 1) ** 2
+    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) <= K:
+        raise ValueError('min_count must be an int in [1, %d] (got %r)' % (K, min_count))
+    shape = tuple(maps.shape)
+    if weight is not None:
+        if isinstance(weight, np.ndarray):
+            if weight.dtype != np.float64:
+                raise ValueError('weight must be float64')
+            weight = torch.from_numpy(np.ascontiguousarray(weight)).to(maps.device)
+        if not (isinstance(weight, torch.Tensor) and weight.device == maps.device and weight.dtype == torch.float64):
+            raise ValueError('weight must be a float64 tensor on maps\' device')
+        if tuple(weight.shape) not in (shape, shape[-2:]):
+            raise ValueError('weight must be [H][W] or of maps\' shape')
+    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
+                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    with _on(stream):
+        if out is not None and out.data_ptr() == maps.data_ptr():
+            src = out
+        else:
+            src = maps.contiguous()
+            if out is None:
+                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        changed = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_changed else None
+        if maps.numel():      # (no cell, nothing to filter)
+            lib = L.load()
+            nbytes = lib.dm_median_bytes(M, H, W)
+            if not nbytes:
+                raise NotImplementedError('median_filter does not take %d maps of %d x %d cells' % (M, H, W))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            w = weight.contiguous() if weight is not None else None
+            wmaps = M if w is not None and w.dim() == 3 else 1
+            L.check(lib.dm_median_filter(L.ptr(src), L.ptr(w), wmaps, M, H, W, radius, int(min_count), iters,
+                                         L.DM_MEDIAN_FILL if fill else 0, L.ptr(out), L.ptr(changed), L.ptr(work),
+                                         L.stream_handle()), 'dm_median_filter')
+    return (out, changed) if return_changed else out
+
+
+def median_weight(median_weight, maps):
+    """The weight plane of ``median=`` for the stitched ``maps`` tuple: None, or with
+    'correlation' the stitched out_map (maps[1]), shared by all modes."""
+    return maps[1] if median_weight == 'correlation' else None

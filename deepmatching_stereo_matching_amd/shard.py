@@ -384,7 +384,8 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         filtering_mode='average', device=None, solver=None, stitcher=None,
                         result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
                         merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
-                        smooth=None, smooth_guide='image', smoother=None):
+                        smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
+                        medianer=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -417,9 +418,18 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     the fill, all modes in one call (engine.bilateral_filter, or ``smoother(d_map, guide or None,
     radius, sigma_color, sigma_space) -> d_map``).  ``smooth_guide``: 'image' -- the guide is
     img1[e:e + H, e:e + W] as uint8, e = (window_size - 1) // 2, the pixel under each map cell
-    -- or 'self'.  Holes stay holes; no tensor is added.  None: nothing changes."""
+    -- or 'self'.  Holes stay holes; no tensor is added.  None: nothing changes.
+    ``median``: a radius, (radius,) or (radius, iters); rank 0 then median filters d_map first,
+    immediately after the stitch and before the speckle filter, the fill and the smoothing, all
+    modes in one call (engine.median_filter, or ``medianer(d_map, weight or None, radius, iters) ->
+    d_map``).  ``median_weight``: None -- the unweighted median -- or 'correlation' -- weighted by
+    the stitched out_map, shared by all modes.  Holes stay holes; no tensor is added.  None:
+    nothing changes.  The chain is stitch -> median -> speckle -> fill -> smooth."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
+    med = engine.median_params(median) if median is not None else None
+    if median_weight not in (None, 'correlation'):
+        raise ValueError("median_weight must be None or 'correlation'")
     iters = engine.fill_iterations(fill) if fill is not None else None
     spk = engine.speckle_params(speckle) if speckle is not None else None
     smo = engine.smooth_params(smooth) if smooth is not None else None
@@ -454,6 +464,13 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     else:
         stitch = stitcher or engine.stitch
         maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
+    if med is not None and maps is not None:
+        weight = engine.median_weight(median_weight, maps)
+        if medianer is not None:
+            d = medianer(maps[0], weight, *med)
+        else:
+            d = engine.median_filter(maps[0], med[0], weight=weight, iters=med[1], out=maps[0])
+        maps = (d,) + tuple(maps[1:])
     if spk is not None:
         nmaps += 1
         if maps is not None:

@@ -418,6 +418,63 @@ int dm_bilateral_filter(const double *d_in, const void *d_guide /* may be NULL *
                         int32_t iters, int32_t flags, double *d_out, uint8_t *d_filled /* may be NULL */,
                         void *d_work, void *stream);
 
+/* ---- Weighted median filter (dm_median.hip) ----------------------------------------------
+ * Not in the reference, whose filtering_mode = 'median' (Matching._filter) works inside one
+ * tile, on integer correspondences, before the stitch.  dm_median_filter is the impulse filter
+ * of the stitched map: dm_filter_speckles only turns outliers into holes, and only those that
+ * form a segment of their own, and dm_bilateral_filter spreads a wrong cell over its
+ * neighbours.  It filters each of the M maps of d_in [M][H][W] on its own.  One pass, with
+ * input X:
+ *   key      the order-preserving 64-bit integer of a double: with the sign bit set all bits
+ *            are flipped, otherwise the sign bit is set.  -0.0 sorts before +0.0 and equal keys
+ *            mean equal bits; "smaller" and "larger" below are by key
+ *   finite   a cell that passes the range test made on the double; NaN and +-inf are holes, as
+ *            in dm_fill_holes
+ *   weights  d_weight NULL: the unweighted form.  Otherwise float64, [H][W] shared by all maps
+ *            (weight_maps == 1) or [M][H][W] (weight_maps == M), the same in every pass
+ *   usable   a tap inside the map at which X is finite and, with weights, the weight w
+ *            satisfies w > 0 && w < +inf (a NaN weight is not usable)
+ *   cell     X[i, j] a hole and DM_MEDIAN_FILL not set: the output is X[i, j] bit for bit.
+ *            Otherwise take the usable taps of the (2r + 1)^2 window clipped to the map in
+ *            window order, dy = -r .. r outer, dx = -r .. r inner, both ascending; n is their
+ *            number.  n < min_count: the output is X[i, j] bit for bit.  Else
+ *              unweighted  the tap value of rank (n - 1) / 2 (0-based, ascending): the lower
+ *                          median
+ *              weighted    T = the float64 sum of the usable taps' weights in window order,
+ *                          from 0.0, one rounding per addition, no contraction; S(v) = the sum
+ *                          formed the same way, in the same order, over the usable taps whose
+ *                          key <= key(v); the output is the smallest tap value v with
+ *                          S(v) >= 0.5 * T
+ *            S is monotone in v (floating-point addition is monotone, and a superset of
+ *            non-negative terms added in the same order never sums lower) and S(max) = T, so
+ *            the smallest such v exists and a bisection over keys finds it.  With all weights
+ *            1.0 the weighted rule equals the unweighted one bit for bit.
+ *   FILL     DM_MEDIAN_FILL: a hole with n >= min_count usable taps receives the median.
+ * `iters` passes, pass k + 1 reading pass k's output.  It follows that every finite output is
+ * bit-identical to some input cell of its window, that without FILL a hole stays
+ * bit-identical, that a map that is all holes comes out as it went in, and that the outputs
+ * are bit-identical from run to run (a thread selects its own cell's value; no atomics).
+ * tests/test_median_host.py restates this in plain loops; the kernel equals it bit for bit. */
+enum { DM_MEDIAN_FILL = 1 };
+
+/* Bytes of the workspace dm_median_filter needs for M maps of H x W cells; 0 for a shape it
+ * does not take (dm_fill_bytes' limits: a count below 1, H W > 2^31 - 1, M > 65535, a side
+ * above 64 * 65535). */
+size_t dm_median_bytes(int32_t M, int32_t H, int32_t W);
+
+/* d_out [M][H][W] may equal d_in (in place).  d_changed ([M][H][W] uint8, may be NULL)
+ * receives 1 where the output's bits differ from d_in's, else 0.  d_work:
+ * dm_median_bytes(M, H, W) bytes, 16-byte aligned, contents arbitrary.  1 <= radius <= 7,
+ * 1 <= iters <= 64, 1 <= min_count <= (2 radius + 1)^2.  DM_ERR_ARG for a null d_in / d_out /
+ * d_work, a count below 1, radius, iters or min_count out of range, unknown flag bits,
+ * weight_maps not 1 or M when weights are given; DM_ERR_UNSUPPORTED for the other shapes
+ * dm_median_bytes refuses.  Validation precedes every HIP call; nothing is allocated, nothing
+ * synchronises, all work goes on `stream`. */
+int dm_median_filter(const double *d_in, const double *d_weight /* may be NULL */, int32_t weight_maps,
+                     int32_t M, int32_t H, int32_t W, int32_t radius, int32_t min_count, int32_t iters,
+                     int32_t flags, double *d_out, uint8_t *d_changed /* may be NULL */,
+                     void *d_work, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -499,9 +556,9 @@ const char *dm_last_error(void);
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
- * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes and
- * dm_bilateral_filter are additive entries within 1.10: no existing entry, struct or workspace
- * changed, so the version stays 110. */
+ * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
+ * dm_bilateral_filter, dm_median_bytes and dm_median_filter are additive entries within 1.10:
+ * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);
 
 #ifdef __cplusplus

@@ -67,6 +67,8 @@ SIGNATURES = {
     'dm_rectify': ([_P, ctypes.c_size_t, _P, _P], ctypes.c_int),
     'dm_rectify64': ([_P, ctypes.c_size_t, _P, _P], ctypes.c_int),
     'dm_pow14_variant': ([_I, _P, ctypes.c_size_t, _P, _P], ctypes.c_int),
+    'dm_debug_num_tile_f16': ([_P, _P, _I, _P, _P], ctypes.c_int),
+    'dm_level_num_f16': ([_TP], ctypes.c_int),
     'dm_aggregate': ([_P, _I, _I, _I, _I, _P, _P], ctypes.c_int),
     'dm_match': ([_TP, _P, ctypes.POINTER(ctypes.c_void_p), _I, _I, _I, _I, _I, _I, _I, _I,
                   _P, _P, _P], ctypes.c_int),

@@ -1364,6 +1364,21 @@ static bool strip2_shape(const dm_tiles *b)
     return strip_shape(b) && ((DM_S2 >> (b->w0 == 64 ? 0 : b->w0 == 128 ? 1 : 2)) & 1);
 }
 
+// num whole from the f16 MFMA in sweep 2 (dm_mfma.h, num_tile_f16): the w0 = 128 instance of
+// k_level1_mfq (C3).  THE predicate for the window-operand layout of a batch: dm_corr_stats
+// writes the binary16 operands and the b_q plane where it holds (k_prep_windows16<WSC, true>),
+// launch_mfq_t launches the F16 instance where it holds, and nothing else reads region 1 of
+// such a batch (the volume kernels prep their own region, the pruned kernel is excluded).  The
+// workspace size is the same under both layouts (the b_q plane is half the QS region), so
+// dm_stats_bytes does not ask.
+#ifndef DM_F16Y
+#define DM_F16Y 1   // 0: the i8 tiles and the three-step y (A/B build switch)
+#endif
+static bool f16y_shape(const dm_tiles *b)
+{
+    return DM_F16Y && !DM_PRUNE && strip_shape(b) && !strip2_shape(b) && b->w0 == 128;
+}
+
 static size_t strip_bytes(const dm_tiles *b)
 {
     const size_t rows = (size_t)b->T * (b->h0 / 2);
@@ -1605,6 +1620,9 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
         // level 1 not stored: the child pows pruned to the level-2 window maxima (dm_prune.h;
         // DM_PRUNE, off: measured slower)
         else if (prune_c3<L2F && YF>(gg, s, L1, L2, Bw, QS, Bs, Ss, grid / NBc, st)) {}
+        else if (f16y_shape(b)) {
+            if constexpr (YF) k_level1_mfq<1, 4, 2 * NBc, DM_C3_MINW, L2F, YF, NBc, CL, YF, YF><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
+        }
         else if (Bs) k_level1_mfq<1, 4, 2 * NBc, DM_C3_MINW, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
         else k_level1_mfq<1, 4, 2 * NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
         HIP_TRY(hipGetLastError());
@@ -1791,7 +1809,7 @@ int dm_abi_version(void) { return 110; }
 #define DM_STR(x) DM_STR2(x)
 const char *dm_build_config(void)
 {
-    return "S1=" DM_STR(DM_S1) " S2=" DM_STR(DM_S2) " PRUNE=" DM_STR(DM_PRUNE) " STRIP_WAVESYNC=" DM_STR(DM_STRIP_WAVESYNC) " VS1=" DM_STR(DM_VS1) " VS1_LDS=" DM_STR(DM_VS1_LDS) " XCD_MAP=" DM_STR(DM_XCD_MAP) " C2_NB=" DM_STR(DM_C2_NB) " C3_NB=" DM_STR(DM_C3_NB) " C3_MW=" DM_STR(DM_C3_MW) " C3_MINW=" DM_STR(DM_C3_MINW) " C5_NB=" DM_STR(DM_C5_NB)
+    return "S1=" DM_STR(DM_S1) " F16Y=" DM_STR(DM_F16Y) " S2=" DM_STR(DM_S2) " PRUNE=" DM_STR(DM_PRUNE) " STRIP_WAVESYNC=" DM_STR(DM_STRIP_WAVESYNC) " VS1=" DM_STR(DM_VS1) " VS1_LDS=" DM_STR(DM_VS1_LDS) " XCD_MAP=" DM_STR(DM_XCD_MAP) " C2_NB=" DM_STR(DM_C2_NB) " C3_NB=" DM_STR(DM_C3_NB) " C3_MW=" DM_STR(DM_C3_MW) " C3_MINW=" DM_STR(DM_C3_MINW) " C5_NB=" DM_STR(DM_C5_NB)
            " VL_H_TR=" DM_STR(DM_VL_H_TR) " VL_H_NT=" DM_STR(DM_VL_H_NT) " VL_H_NW=" DM_STR(DM_VL_H_NW)
            " VL_H2_TR=" DM_STR(DM_VL_H2_TR) " VL_H2_NW=" DM_STR(DM_VL_H2_NW) " VL_F2_TR=" DM_STR(DM_VL_F2_TR)
            " VL_F2_MW=" DM_STR(DM_VL_F2_MW) " VL_HS_NW=" DM_STR(DM_VL_HS_NW) " VL_HS_TR=" DM_STR(DM_VL_HS_TR) " VL_F_NW=" DM_STR(DM_VL_F_NW)
@@ -1824,6 +1842,12 @@ size_t dm_stats_bytes(const dm_tiles *b)
     return tot;
 }
 
+int dm_level_num_f16(const dm_tiles *b)
+{
+    if (!b || b->ws < 1 || b->ws > 15 || b->T <= 0 || b->h0 <= 0 || b->w0 <= 0) return 0;
+    return f16y_shape(b) ? 1 : 0;
+}
+
 int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
 {
     int rc = check_tiles(b);
@@ -1841,7 +1865,11 @@ int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
         const int G = b->w0 / 16, KS = (b->ws * b->ws + 63) / 64;
         const size_t n = (size_t)b->T * b->h0 * G * 16;
         const int GW = G / mfq_nw(b);
-        if (!strip2_shape(b)) {
+        if (f16y_shape(b)) {
+            if (b->ws == 5) k_prep_windows16<5, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
+            else k_prep_windows16<0, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
+            HIP_TRY(hipGetLastError());
+        } else if (!strip2_shape(b)) {
             if (b->ws == 5) k_prep_windows16<5><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             else k_prep_windows16<0><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             HIP_TRY(hipGetLastError());
@@ -1992,6 +2020,17 @@ int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_ou
     case DM_POW_FULL: k_pow_variant<DM_POW_FULL><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     default: return fail(DM_ERR_ARG, "unknown pow14 variant %d", variant);
     }
+    HIP_TRY(hipGetLastError());
+    return DM_OK;
+}
+
+int dm_debug_num_tile_f16(const uint8_t *d_patch_taps, const uint8_t *d_window_taps, int32_t ws,
+                          float *d_num, void *stream)
+{
+    if (!d_patch_taps || !d_window_taps || !d_num) return fail(DM_ERR_ARG, "null taps / output");
+    // n + 4 K slots of the 32: ws <= 5 (num_tile_f16 in dm_mfma.h)
+    if (ws != 1 && ws != 3 && ws != 5) return fail(DM_ERR_UNSUPPORTED, "window side %d: the f16 num tile takes 1, 3 or 5", ws);
+    k_debug_num_tile_f16<<<1, 64, 0, (hipStream_t)stream>>>(d_patch_taps, d_window_taps, ws, d_num);
     HIP_TRY(hipGetLastError());
     return DM_OK;
 }

@@ -16,6 +16,100 @@
 typedef int dm_v4i __attribute__((ext_vector_type(4)));
 typedef int dm_v2i __attribute__((ext_vector_type(2)));
 
+// ABLATION ONLY (tools/abl_build.sh f16y; results WRONG): the price of taking num from the
+// f16 MFMA (num_tile_f16 below) in sweep 2 before that is built -- sweep 2 of the strip-sweep
+// instances of k_level1_mfq feeds today's i8 fragments to v_mfma_f32_16x16x32_f16 and takes y
+// as the one packed multiply D * b_q.  Bit 14 of every binary16 half of the operands is
+// cleared (the patch operand in the kernel, once per wave; the window operands where
+// k_prep_windows16 writes them) so that none is an infinity or a NaN: the values are
+// meaningless but finite, and the kernel's instruction stream is the one being priced.
+#ifndef DM_ABL_F16Y
+#define DM_ABL_F16Y 0
+#endif
+#define DM_ABL_F16_FINITE ((int)0xBFFFBFFF)
+
+// ===================================================================================
+// num = n sum_k T'_k I'_k - sT sI as ONE v_mfma_f32_16x16x32_f16 (ws <= 5), exact.
+// The i8 MFMA returns the dot product only, and y_of_acc spends two packed-f32 steps per
+// pair of voxels on n * acc - sT * sI.  The f16 form has the same 16 x 16 result layout and
+// 16-byte operands (lane c + 16 hq: K slots 8 hq .. 8 hq + 7, as the spread layout) and a
+// float32 accumulator, and binary16 holds every integer of magnitude <= 2048, so the whole
+// of num fits into its K = 32 slots:
+//   slots 0 .. n-1     patch ws * T'_k, window ws * I'_k: |.| <= 5 * 128 = 640, product
+//                      n T'_k I'_k
+//   slots n .. n+3     the sums as two digits, s = hi + lo with hi = 64 floor(s / 64) (a
+//                      multiple of 64 of magnitude <= 3200: exact in binary16) and lo in
+//                      [0, 63]: patch (Thi, Thi, Tlo, Tlo) against window (-Ihi, -Ilo, -Ihi,
+//                      -Ilo), four products that sum to -(Thi + Tlo)(Ihi + Ilo) = -sT sI
+//   the rest           zero (n + 4 = 29 of 32 slots at ws = 5, 13 at ws = 3)
+// Every term is an integer, and whatever order or grouping the hardware adds them in, a
+// partial sum lies between minus the mass of the negative terms and the mass of the
+// positive ones; both masses are below 2^24 (<= 15,523,662 at ws = 5),
+// so every partial sum is an integer a float32 holds exactly and D = num -- given that the
+// matrix core returns the exact sum when every partial sum is representable, which
+// dm_debug_num_tile_f16 (tests/test_f16_num.py) checks against int64 arithmetic on the
+// device through exactly these helpers.  C is the inline constant 0; y = D * b_q is then the
+// formula's one rounding.
+// ===================================================================================
+typedef _Float16 dm_v8h __attribute__((ext_vector_type(8)));
+typedef float dm_v4f __attribute__((ext_vector_type(4)));
+
+// K slot k of the patch (WIN = false) or window (WIN = true) operand, as an integer: `tap`
+// is T'_k / I'_k (read for k < n only), s the sum of the n taps
+template <bool WIN>
+__device__ __forceinline__ int f16_slot(int k, int n, int ws, int tap, int s)
+{
+    if (k < n) return ws * tap;
+    const int j = k - n;
+    if (j >= 4) return 0;
+    const int lo = s & 63, hi = s - lo;   // hi = 64 floor(s / 64), two's complement
+    if (WIN) return (j & 1) ? -lo : -hi;
+    return (j & 2) ? lo : hi;
+}
+
+// the 16 operand bytes of lane group hq: slots 8 hq .. 8 hq + 7 as binary16 (the int ->
+// binary16 conversions are exact, see above); tap(k) is called for k < n only
+template <bool WIN, typename F>
+__device__ __forceinline__ dm_v4i f16_frag(F tap, int s, int n, int ws, int hq)
+{
+    int w[4];
+#pragma unroll
+    for (int j = 0; j < 8; j += 2) {
+        unsigned h[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const int k = 8 * hq + j + e;
+            const _Float16 v = (_Float16)f16_slot<WIN>(k, n, ws, k < n ? tap(k) : 0, s);
+            h[e] = __builtin_bit_cast(unsigned short, v);
+        }
+        w[j >> 1] = (int)(h[0] | (h[1] << 16));
+    }
+    return dm_v4i{w[0], w[1], w[2], w[3]};
+}
+
+// D[reg] = num(patch row 4 (lane >> 4) + reg, window column lane & 15)
+__device__ __forceinline__ dm_v4f num_tile_f16(const dm_v4i &a, const dm_v4i &b)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dm_v8h, a), __builtin_bit_cast(dm_v8h, b),
+                                                  dm_v4f{0.0f, 0.0f, 0.0f, 0.0f}, 0, 0, 0);
+}
+
+// dm_debug_num_tile_f16: one wave, 16 patches x 16 windows of n = ws * ws uint8 taps each
+// ([16][n], tap k = ws * row + column); out[16 * patch + window] = num
+__global__ __launch_bounds__(64) void k_debug_num_tile_f16(const uint8_t *__restrict__ pt,
+                                                           const uint8_t *__restrict__ wt, int ws, float *out)
+{
+    const int lane = threadIdx.x & 63, c = lane & 15, hq = lane >> 4, n = ws * ws;
+    auto tp = [&](int k) { return (int)pt[c * n + k] - 128; };
+    auto tw = [&](int k) { return (int)wt[c * n + k] - 128; };
+    int sT = 0, sI = 0;
+    for (int k = 0; k < n; ++k) { sT += tp(k); sI += tw(k); }
+    const dm_v4f d = num_tile_f16(f16_frag<false>(tp, sT, n, ws, hq), f16_frag<true>(tw, sI, n, ws, hq));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) out[16 * (4 * hq + r) + c] = d[r];
+}
+
+
 // ===================================================================================
 // 16x16x64 variant (default).  v_mfma_i32_16x16x64_i8: lane L holds A[row L&15][k = 64ks +
 // 16(L>>4) + j] and B[k][col L&15]; acc[reg] = C[row 4(L>>4) + reg][col L&15].
@@ -35,7 +129,12 @@ typedef int dm_v2i __attribute__((ext_vector_type(2)));
 // k_level1_mfq; GW = 16 B of output per lane for k_volume_ls.
 // WSC: window side known at compile time (0 = g.ws): the window's bytes are loaded once and
 // serve both the sums and the fragments.
-template <int WSC>
+// F16 (f16y_shape: KS == 1, ws <= 5, GW == 4): the same Bw indexing, but all 16 bytes of a lane
+// are K data -- the binary16 window operand of num_tile_f16, slots 8 hq .. 8 hq + 7 (ws * I' in
+// slots 0 .. n-1, the negated digits of sum(I') in n .. n+3) -- and the QS region holds b_q
+// alone as a float32 plane [t][q0][q1]: lane c's four tiles of column group w are windows
+// 64 w + 4 c + 0 .. 3, one 16-byte load per lane and row (sum(I') is inside the product).
+template <int WSC, bool F16 = false>
 __global__ void k_prep_windows16(Geo g, int G, int GW, int KS, dm_v4i *Bw, int2 *QS)
 {
     DM_TAIL_ENTRY();
@@ -70,8 +169,14 @@ __global__ void k_prep_windows16(Geo g, int G, int GW, int KS, dm_v4i *Bw, int2 
     if (g.method == DM_TM_CCOEFF) bq = 1.0f;
     else bq = dI == 0 ? 0.0f : (float)(1.0 / sqrt((double)dI));
     const int qx = __float_as_int((float)-s), qy = __float_as_int(bq); // exact: |s| <= 225*128
-    QS[idx] = make_int2(qx, qy);
     const size_t tile = idx / 16; // (t, q0, tau)
+    if constexpr (F16) {
+        ((float *)QS)[((size_t)t * g.h0 + q0) * g.w0 + q1] = bq;
+#pragma unroll
+        for (int hq = 0; hq < 4; ++hq) Bw[tile * 64 + c + 16 * hq] = f16_frag<true>(px, s, n, ws, hq);
+        return;
+    }
+    QS[idx] = make_int2(qx, qy);
     // spread layout (KS == 1, n <= 32; build_a uses the same): lane c + 16 hq holds taps
     // 8 hq .. 8 hq + 7 in bytes 0..7 and the window's stats {qx, qy} in words 2, 3, which meet
     // A's zero bytes 8..15 -- every lane reads its own window's stats from its own fragment
@@ -88,6 +193,10 @@ __global__ void k_prep_windows16(Geo g, int G, int GW, int KS, dm_v4i *Bw, int2 
                 }
                 w[2] = qx;
                 w[3] = qy;
+#if DM_ABL_F16Y
+                // ABLATION ONLY: finite binary16 halves (qx's already are: |s| < 2^12)
+                w[0] &= DM_ABL_F16_FINITE; w[1] &= DM_ABL_F16_FINITE; w[3] &= (int)0xFFFFBFFF;
+#endif
             } else {
                 for (int j = 0; j < 16; ++j) {
                     const int k = 64 * ks + 16 * hq + j;
@@ -545,13 +654,18 @@ struct XchOwn<true, T, OFF> {
 // half the matrix-core issue cycles of the 16 x 16 tiles per voxel (A rows from the LDS tap table,
 // fill_ptab), and the window stats
 // broadcast without copies; sweep 2 keeps the 16 x 16 layout its pooling needs.
-template <int KS, int GW, int NW, int MINW, bool L2F, bool YF, int NB = 1, bool CL = false, bool S1 = false>
+// F16 (with S1; k_prep_windows16<WSC, true> wrote Bw / QS): sweep 2 takes num whole from the f16
+// MFMA (num_tile_f16) and y = num * b_q is one packed multiply per two voxels -- no accumulator
+// bias, no patch sums in registers, b_q from the float32 plane in QS.
+template <int KS, int GW, int NW, int MINW, bool L2F, bool YF, int NB = 1, bool CL = false, bool S1 = false,
+          bool F16 = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, const dm_v4i *__restrict__ Bw,
                                                         const int2 *__restrict__ QS, double *L1, double *L2,
                                                         const dm_v4i *__restrict__ Bs = nullptr,
                                                         const dm_v4i *__restrict__ Ss = nullptr)
 {
     DM_CLOCK_STAMP_HERE
+    static_assert(!F16 || (S1 && KS == 1 && GW == 4 && YF), "f16 num: strip sweep 1, one 16-byte b_q load per lane and row");
     constexpr bool EQ = KS == 1 && YF;           // window stats ride in the B tile (qs_of_frag)
     static_assert(NW % NB == 0, "blocks split the waves evenly");
     static_assert(!CL || L2F, "clamp-bit normalisation: NaN cells are restored at the level-2 / level-1 stores");
@@ -624,9 +738,25 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
     // the 16 x 16 tiles' patch operand and sums (S1: built after the strip sweep, which does
     // not read them -- they would hold registers through it)
     auto init_a16 = [&]() {
+        if constexpr (F16) {
+            // the binary16 patch operand of num_tile_f16, slots 8 grp .. 8 grp + 7 of patch row c:
+            // ws * T' from the int8 taps of ptab, the digits of the patch's sum (s.sT) behind them
+            const dm_v2i tp = *(const dm_v2i *)&ptab[sb][c][2 * grp];
+            const int cl = c >> 2, ch = c & 3;
+            const int pa = (2 * (I0 + (cl >> 1)) + (ch >> 1)) * w0 + 2 * (J0 + (cl & 1)) + (ch & 1);
+            auto tap = [&](int k) {
+                const int j = k - 8 * grp; // 0 .. 7
+                return (int)(signed char)(((unsigned)(j < 4 ? tp.x : tp.y)) >> (8 * (j & 3)));
+            };
+            A[0] = f16_frag<false>(tap, s.sT[tb + pa], n, g.ws, grp);
+            return; // the patch sums are inside the product
+        }
         if constexpr (S1) { // the spread fragment: taps 8 grp .. 8 grp + 7 of patch row c (ptab)
             const dm_v2i tp = *(const dm_v2i *)&ptab[sb][c][2 * grp];
             A[0] = dm_v4i{tp.x, tp.y, 0, 0};
+#if DM_ABL_F16Y
+            A[0].x &= DM_ABL_F16_FINITE; A[0].y &= DM_ABL_F16_FINITE; // ABLATION ONLY
+#endif
         } else {
             build_a<KS>(A, g, t, I0, J0, c, grp);
         }
@@ -650,13 +780,18 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
     struct RowFrag {
         dm_v4i b[GW][KS];
         int2 q[GW];
+        dm_v4f bq;   // F16: b_q of the lane's GW = 4 windows (tiles tw = 0 .. 3)
     };
     // buffer loads: wave-uniform resource + row offset in SGPRs, lane offset a constant
     // VGPR -- no per-load VALU address arithmetic
     const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void *)Bt, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void *)Qt, 0, 0x7fffffff, 0x00020000);
-    const unsigned voB = (unsigned)lane * 16u, voQ = (unsigned)c * 8u;
+    // F16: the b_q plane [t][q0][q1] (k_prep_windows16<WSC, true>), this wave's 16 GW columns
+    const void *Qb = F16 ? (const void *)((const float *)QS + (size_t)t * P + 16 * GW * wc) : (const void *)Qt;
+    const __amdgpu_buffer_rsrc_t rQ = __builtin_amdgcn_make_buffer_rsrc((void *)Qb, 0, 0x7fffffff, 0x00020000);
+    const unsigned voB = (unsigned)lane * 16u, voQ = F16 ? (unsigned)c * 16u : (unsigned)c * 8u;
     auto load_row = [&](RowFrag &f, int q0) {
+        if constexpr (F16)
+            f.bq = __builtin_bit_cast(dm_v4f, __builtin_amdgcn_raw_buffer_load_b128(rQ, voQ, (unsigned)(q0 * w0) * 4u, 0));
 #pragma unroll
         for (int tw = 0; tw < GW; ++tw) {
             const unsigned ti = (unsigned)q0 * G + tw;
@@ -828,9 +963,30 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
     auto pool_cols = [&](const RowFrag &f, float (&Cm)[M][4], float (&last)[4]) {
 #pragma unroll
         for (int tw = 0; tw < GW; ++tw) {
-            const dm_v4i acc = mfma_tile<KS, EQ>(A, f.b[tw], acc0);
             float y[4];
-            y_of_acc<YF>(acc, sTr, sTf, EQ ? qs_of_frag(f.b[tw][0]) : qs_pair(f.q[tw]), n, y);
+            if constexpr (F16) { // num whole from the f16 MFMA; y = num * b_q, the one rounding
+                const dm_v4f d = num_tile_f16(A[0], f.b[tw][0]);
+                const dm_f2 q2 = tw < 2 ? dm_f2{f.bq[0], f.bq[1]} : dm_f2{f.bq[2], f.bq[3]};
+                // (tw is a constant after unrolling.  Plain multiplies, not pk_mul_bhi: the compiler
+                // pads the MFMA -> VALU read hazard for its own instructions only, and an asm
+                // statement reading D right behind the MFMA gets stale registers)
+                const dm_f2 bb = (tw & 1) ? __builtin_shufflevector(q2, q2, 1, 1) : __builtin_shufflevector(q2, q2, 0, 0);
+                const dm_f2 y01 = dm_f2{d[0], d[1]} * bb, y23 = dm_f2{d[2], d[3]} * bb;
+                y[0] = y01.x; y[1] = y01.y; y[2] = y23.x; y[3] = y23.y;
+            } else
+#if DM_ABL_F16Y
+            if constexpr (S1 && EQ) { // ABLATION ONLY (results wrong): f16 MFMA, y = D * b_q
+                const dm_v4f d = num_tile_f16(A[0], f.b[tw][0]);
+                const dm_f2 q2 = qs_of_frag(f.b[tw][0]);
+                const dm_f2 bb = __builtin_shufflevector(q2, q2, 1, 1);   // (no asm on D: see F16 above)
+                const dm_f2 y01 = dm_f2{d[0], d[1]} * bb, y23 = dm_f2{d[2], d[3]} * bb;
+                y[0] = y01.x; y[1] = y01.y; y[2] = y23.x; y[3] = y23.y;
+            } else
+#endif
+            {
+                const dm_v4i acc = mfma_tile<KS, EQ>(A, f.b[tw], acc0);
+                y_of_acc<YF>(acc, sTr, sTf, EQ ? qs_of_frag(f.b[tw][0]) : qs_pair(f.q[tw]), n, y);
+            }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 if ((tw & 1) == 0) Cm[tw / 2][r] = tw == 0 ? y[r] : fmaxf(last[r], y[r]);

@@ -151,6 +151,21 @@ int dm_rectify64(const double *d_in, size_t n, double *d_out, void *stream);
 enum dm_pow_variant { DM_POW_F32 = 0, DM_POW_Q4 = 1, DM_POW_K = 2, DM_POW_FULL = 3, DM_POW_Q4G = 4, DM_POW_KG = 5 };
 int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_out, void *stream);
 
+/* Self-test of the exact float32 num = n * sum_k T'_k I'_k - sum(T') * sum(I') from ONE
+ * v_mfma_f32_16x16x32_f16 (csrc/dm_mfma.h, num_tile_f16), through the device helpers a level
+ * kernel would use: the binary16 operand builders, the digit split of the sums and the MFMA
+ * call.  d_patch_taps / d_window_taps: uint8 [16][ws*ws] (tap k = ws * row + column; T' and
+ * I' are the bytes - 128); d_num: float32 [16 patches][16 windows].  ws in {1, 3, 5}
+ * (ws*ws + 4 of the instruction's 32 K slots).  Every d_num equals the integer exactly. */
+int dm_debug_num_tile_f16(const uint8_t *d_patch_taps, const uint8_t *d_window_taps, int32_t ws,
+                          float *d_num, void *stream);
+
+/* 1 when the level kernel of this batch (dm_corr_level1 / dm_corr_level12) takes num from the
+ * f16 MFMA in its second sweep, 0 otherwise: the one predicate by which dm_corr_stats chooses
+ * the window-operand layout and the launcher the kernel instance (w0 = 128, ws <= 5,
+ * h0 % 4 == 0 in a default build).  Reads the shape fields of *b only, no device memory. */
+int dm_level_num_f16(const dm_tiles *b);
+
 /* One pyramid step for levels >= 1: MaxPool2d(3,2,1) per map, (ul+ur+ll+lr)/4, and
  * (rectify != 0) the 1.4 power.  d_in float64 [T][h*w][h*w] -> d_out float64
  * [T][(h/2)*(w/2)][(h/2)*(w/2)].
@@ -557,7 +572,8 @@ const char *dm_last_error(void);
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
- * dm_bilateral_filter, dm_median_bytes and dm_median_filter are additive entries within 1.10:
+ * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16 and
+ * dm_level_num_f16 are additive entries within 1.10:
  * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);
 

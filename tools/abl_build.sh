@@ -10,6 +10,11 @@
 #           barriers between the sweeps, as in round 5 (DM_STRIP_WAVESYNC=0; results exact)
 #   prune0, prune1  (round 6) the C3 level kernel without / with the child-pow pruning
 #           (k_level1_mfq / k_level12_prune, DM_PRUNE; results exact)
+#   f16y    sweep 2 of the C3 k_level1_mfq on v_mfma_f32_16x16x32_f16 with y = D * b_q as one packed
+#           multiply, fed today's i8 fragments (DM_ABL_F16Y): the floor of taking num from the f16
+#           MFMA (dm_mfma.h, num_tile_f16) before the operands are built (results wrong)
+#   f16y0   the C3 k_level1_mfq with the i8 tiles and the three-step y in sweep 2, as before num
+#           came from the f16 MFMA (DM_F16Y=0; results exact)
 #   nosw1   sweep 1 (per-patch min / max) skipped
 #   pconst  pow14_zf's three LDS table reads at fixed rows (broadcast: no bank conflicts)
 #   pnoread pow14_zf without its LDS table reads (values from the index bits, no LDS)
@@ -70,6 +75,8 @@ open(p, 'w').write(s)
 PY
     ;;
     papprox) EXTRA="-DDM_ABL_PAPPROX=1" ;;
+    f16y) EXTRA="-DDM_F16Y=0 -DDM_ABL_F16Y=1" ;;
+    f16y0) EXTRA="-DDM_F16Y=0" ;;
     ssync) EXTRA="-DDM_STRIP_WAVESYNC=0" ;;
     prune0) EXTRA="-DDM_PRUNE=0" ;;
     prune1) EXTRA="-DDM_PRUNE=1" ;;
@@ -152,7 +159,7 @@ PY
     base) ;;
     *) echo "unknown $v"; exit 2 ;;
   esac
-  (cd $d && /opt/rocm/bin/hipcc $FLAGS $EXTRA -I $r/include csrc/dm_kernels.hip csrc/dm_postproc.hip csrc/dm_fb.hip -o $REPO/ab/libdm_$v.so) &
+  (cd $d && /opt/rocm/bin/hipcc $FLAGS $EXTRA -I $r/include csrc/*.hip -o $REPO/ab/libdm_$v.so) &
 done
 wait
 ls -la $REPO/ab

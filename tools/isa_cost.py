@@ -14,8 +14,10 @@ instruction on one SIMD, many waves):
   14   v_mfma_i32_16x16x64_i8 and 11.2 v_mfma_i32_16x16x32_i8: what one MFMA adds to a stream of
        independent VALU work on its SIMD (profiles/r03_valu_probe.txt: one MFMA + N v_fma_f32 per
        step takes ~13.4 + 2.4 N cycles for K=64 and ~11.2 + 2.2 N for K=32, N = 4..12; both take
-       16 cycles alone)
-  22   v_mfma_i32_32x32x32_i8 (the row-pair strips of sweep 1, round 5): 41.6 cycles with 8
+       16 cycles alone); 14 also v_mfma_f32_16x16x32_f16 with C = 0 (sweep 2 of the C3 level kernel):
+       22.8 / 32.7 / 41.5 cycles with 4 / 8 / 12 v_fma_f32, ~13.5 + 2.3 N, against 22.7 / 32.0 / 42.2
+       for the K = 64 i8 form in the same run (profiles/r07_f16y_valu_probe.txt)
+  22  v_mfma_i32_32x32x32_i8 (the row-pair strips of sweep 1, round 5): 41.6 cycles with 8
        v_fma_f32 and 56.1 with 16 in the same probe, i.e. 24.0 / 20.9 besides their 2.2 each
        (35.9 alone)
 
@@ -40,7 +42,8 @@ def cost(op, line):
     if op.startswith('v_mfma'):
         if '32x32x32' in op:
             return 22.0
-        return 11.2 if '16x16x32' in op else 14.0
+        # v_mfma_f32_16x16x32_f16 (num_tile_f16): as the K = 64 i8 form (same pass count)
+        return 11.2 if '16x16x32_i8' in op else 14.0
     if TRANS.match(op):
         return 8.0
     if CHEAP.match(op) and 'dpp' not in line and '_e64' not in op and not SGPR.search(line.split(None, 1)[-1]):

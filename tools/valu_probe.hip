@@ -2,8 +2,10 @@
 // i32 ops and f32->f64 converts on gfx950, 8 independent chains per lane so the issue rate
 // (not the latency) bounds each loop.  Prints ns per wave-instruction per SIMD.
 //   hipcc -O3 --offload-arch=gfx950 tools/valu_probe.hip -o /tmp/valu_probe && /tmp/valu_probe
+//   /tmp/valu_probe --mfma16    only the 16 x 16 MFMA forms beside 0 / 4 / 8 / 12 v_fma_f32
 #include <hip/hip_runtime.h>
 #include <cstdio>
+#include <cstring>
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 constexpr int ITER = 4096, CH = 8;
@@ -174,7 +176,10 @@ __global__ __launch_bounds__(256) void p_mfma_mix(float *out, float a, float b)
 }
 
 // the same with other MFMA shapes: K = 0 bf16 16x16x32, 1 f16 16x16x32, 2 i8 32x32x32,
-// 3 bf16 32x32x16 (one instruction per step, 4 rotating accumulators)
+// 3 bf16 32x32x16 (one instruction per step, 4 rotating accumulators), 4 i8 16x16x32,
+// 5 f16 16x16x32 with the inline constant 0 as C and 4 rotating destinations (no accumulator
+// read: the form that returns num, dm_mfma.h num_tile_f16; inline asm, or the loop-invariant
+// product would be hoisted)
 template <int K, int NV>
 __global__ __launch_bounds__(256) void p_mfma_mix2(float *out, float a, float b)
 {
@@ -202,6 +207,8 @@ __global__ __launch_bounds__(256) void p_mfma_mix2(float *out, float a, float b)
                 acc4[k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8h, A), __builtin_bit_cast(v8h, B), acc4[k], 0, 0, 0);
             else if constexpr (K == 2)
                 acci[k] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, B, acci[k], 0, 0, 0);
+            else if constexpr (K == 5)
+                asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "+v"(acc4[k]) : "v"(A), "v"(B)); // "+v": 4 live destinations
             else if constexpr (K == 4) {  // i8 16x16x32 (8-byte operands)
                 typedef int v4i_ __attribute__((ext_vector_type(4)));
                 v4i_ r = __builtin_bit_cast(v4i_, acc4[k]);
@@ -214,6 +221,7 @@ __global__ __launch_bounds__(256) void p_mfma_mix2(float *out, float a, float b)
             for (int c = 0; c < NV; ++c) asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(v[c % 8]) : "v"(a), "v"(b));
         }
     }
+    if constexpr (K == 5) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); // the asm MFMAs' results land
     float s = 0; for (int c = 0; c < 8; ++c) s += v[c];
     for (int k = 0; k < 4; ++k) {
         s += acc4[k][0] + accf[k][0] + accf[k][15] + (float)(acci[k][0] + acci[k][15]);
@@ -293,10 +301,22 @@ static void run(const char *name, int insts_per_iter_chain, float *d)
            ghz, ns * ghz);
 }
 
-int main()
+int main(int argc, char **argv)
 {
     float *d;
     hipMalloc(&d, 256 * 8192 * sizeof(float) * 4);
+    if (argc > 1 && !strcmp(argv[1], "--mfma16")) { // the 16 x 16 MFMA forms beside VALU only
+        run_mix("i8_16x16x64", p_mfma_mix<0>, d, 0); run_mix("i8_16x16x64", p_mfma_mix<4>, d, 4);
+        run_mix("i8_16x16x64", p_mfma_mix<8>, d, 8); run_mix("i8_16x16x64", p_mfma_mix<12>, d, 12);
+        run_mix("i8_16x16x32", p_mfma_mix2<4, 0>, d, 0); run_mix("i8_16x16x32", p_mfma_mix2<4, 4>, d, 4);
+        run_mix("i8_16x16x32", p_mfma_mix2<4, 8>, d, 8); run_mix("i8_16x16x32", p_mfma_mix2<4, 12>, d, 12);
+        run_mix("f16_16x32", p_mfma_mix2<1, 0>, d, 0); run_mix("f16_16x32", p_mfma_mix2<1, 4>, d, 4);
+        run_mix("f16_16x32", p_mfma_mix2<1, 8>, d, 8); run_mix("f16_16x32", p_mfma_mix2<1, 12>, d, 12);
+        run_mix("f16_16x32 C=0", p_mfma_mix2<5, 0>, d, 0); run_mix("f16_16x32 C=0", p_mfma_mix2<5, 4>, d, 4);
+        run_mix("f16_16x32 C=0", p_mfma_mix2<5, 8>, d, 8); run_mix("f16_16x32 C=0", p_mfma_mix2<5, 12>, d, 12);
+        hipFree(d);
+        return 0;
+    }
     run<0>("f32_fma", 1, d);
     run<1>("pk_fma_f32", 1, d);
     run<2>("f64_fma", 1, d);
@@ -351,6 +371,9 @@ int main()
     run_mix(nm[4], p_mfma_mix2<4, 0>, d, 0); run_mix(nm[4], p_mfma_mix2<4, 4>, d, 4); run_mix(nm[4], p_mfma_mix2<4, 8>, d, 8);
     run_mix(nm[0], p_mfma_mix2<0, 0>, d, 0); run_mix(nm[0], p_mfma_mix2<0, 4>, d, 4); run_mix(nm[0], p_mfma_mix2<0, 8>, d, 8);
     run_mix(nm[1], p_mfma_mix2<1, 0>, d, 0); run_mix(nm[1], p_mfma_mix2<1, 4>, d, 4); run_mix(nm[1], p_mfma_mix2<1, 8>, d, 8);
+    run_mix(nm[1], p_mfma_mix2<1, 12>, d, 12);
+    run_mix("f16_16x32 C=0", p_mfma_mix2<5, 0>, d, 0); run_mix("f16_16x32 C=0", p_mfma_mix2<5, 4>, d, 4);
+    run_mix("f16_16x32 C=0", p_mfma_mix2<5, 8>, d, 8); run_mix("f16_16x32 C=0", p_mfma_mix2<5, 12>, d, 12);
     run_mix(nm[2], p_mfma_mix2<2, 0>, d, 0); run_mix(nm[2], p_mfma_mix2<2, 8>, d, 8); run_mix(nm[2], p_mfma_mix2<2, 16>, d, 16);
     run_mix(nm[3], p_mfma_mix2<3, 0>, d, 0); run_mix(nm[3], p_mfma_mix2<3, 8>, d, 8); run_mix(nm[3], p_mfma_mix2<3, 16>, d, 16);
     hipFree(d);

@@ -965,3 +965,144 @@ def median_weight(median_weight, maps):
     """The weight plane of ``median=`` for the stitched ``maps`` tuple: None, or with
     'correlation' the stitched out_map (maps[1]), shared by all modes."""
     return maps[1] if median_weight == 'correlation' else None
+
+
+def photo_params(photo):
+    """The ``photo=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius, min_score):
+    an int radius in [1, 7] (the window is (2 radius + 1)^2 pixels) -- the final d_map is scored
+    -- or ``(radius, min_score)`` with min_score a real in [-1, 1]: the cells that score below it
+    are also rejected after the median and before the speckle filter.  min_score is None in the
+    first form."""
+    if isinstance(photo, (tuple, list)):
+        if len(photo) != 2:
+            raise ValueError('photo must be a radius, (radius, min_score) or None')
+        radius, min_score = photo
+        if isinstance(min_score, bool) or not isinstance(min_score, (int, float, np.integer, np.floating)) or \
+                not -1.0 <= float(min_score) <= 1.0:
+            raise ValueError('photo min_score must be a real in [-1, 1] (got %r)' % (min_score,))
+        min_score = float(min_score)
+    else:
+        radius, min_score = photo, None
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
+        raise ValueError('photo radius must be an int in [1, 7] (got %r)' % (radius,))
+    return int(radius), min_score
+
+
+def _photo_image(img, device):
+    """A 2-D uint8 image as a device tensor whose rows are contiguous (the row stride is kept)."""
+    if isinstance(img, torch.Tensor):
+        t = img
+    else:
+        a = np.asarray(img)
+        if a.dtype != np.uint8:
+            raise ValueError('images must be 2-D uint8')
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype != torch.uint8 or t.dim() != 2:
+        raise ValueError('images must be 2-D uint8')
+    t = t.to(device)
+    if t.numel() and (t.stride(1) != 1 or t.stride(0) < t.shape[1]):
+        t = t.contiguous()
+    return t
+
+
+def photo_planes(modes):
+    """Indices (row, column) of 'elevation2' and 'elevation' in a degree_map_mode list: the planes
+    ``photo=`` reads.  ValueError when one is missing."""
+    modes = list(modes)
+    if 'elevation' not in modes or 'elevation2' not in modes:
+        raise ValueError("photo needs both 'elevation' and 'elevation2' in degree_map_mode (got %r)" % (modes,))
+    return modes.index('elevation2'), modes.index('elevation')
+
+
+def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps=None, out=None,
+                return_warped=False, return_rejected=False, stream=None):
+    """Photo-consistency of a disparity map (dm_photo_score).  ``img1``, ``img2``: 2-D uint8
+    images of one shape, numpy arrays or tensors, host or device; a tensor may be a view with a
+    row stride (its rows must be contiguous, else it is copied).  ``d_row``, ``d_col``: float64
+    device tensors [H][W], the 'elevation2' and 'elevation' planes.  ``offset``: an int or
+    (oy, ox); map cell (y, x) is image pixel (y + oy, x + ox).  A cell's score is the zero-mean
+    normalised cross-correlation, in [-1, 1], of the (2 radius + 1)^2 window of img1 around it with
+    img2 resampled bilinearly at (y + oy - d_row, x + ox - d_col); NaN where d_row or d_col is not
+    finite or a window leaves the image; exactly 0.0 where a window is flat.
+    With ``min_score`` (a real in [-1, 1]) ``maps`` -- float64 [H][W] or [M][H][W] on the planes'
+    device -- is required: the cells scoring below it become NaN in every plane, all other cells
+    keep their bits; the result goes to ``out`` if given (``out=maps`` works in place; d_row and
+    d_col may be planes of it), else to a new tensor.
+    -> score [H][W]; with ``min_score`` (score, rejected maps); then, when asked for, the warped
+    plane (img2 resampled at the centre; NaN outside the image) and the uint8 mask of the
+    rejected cells (``return_rejected`` needs ``min_score``) are appended."""
+    for name, d in (('d_row', d_row), ('d_col', d_col)):
+        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.float64 and d.dim() == 2):
+            raise ValueError('%s must be a 2-D float64 device (cuda) tensor' % name)
+    if d_row.shape != d_col.shape or d_row.device != d_col.device:
+        raise ValueError('d_row and d_col must have one shape and device')
+    dev = d_row.device
+    radius = photo_params(radius)[0]
+    if isinstance(offset, (tuple, list)):
+        if len(offset) != 2:
+            raise ValueError('offset must be an int or (oy, ox)')
+        oy, ox = offset
+    else:
+        oy = ox = offset
+    for o in (oy, ox):
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not -2 ** 30 <= int(o) <= 2 ** 30:
+            raise ValueError('offset must be an int or (oy, ox) in [-2^30, 2^30] (got %r)' % (offset,))
+    if min_score is not None:
+        min_score = photo_params((radius, min_score))[1]
+        if not (isinstance(maps, torch.Tensor) and maps.device == dev and maps.dtype == torch.float64 and
+                maps.dim() in (2, 3) and maps.shape[-2:] == d_row.shape):
+            raise ValueError('min_score needs maps: a float64 tensor [H][W] or [M][H][W] on the planes\' device')
+        if out is not None and not (isinstance(out, torch.Tensor) and out.device == dev and
+                                    out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+            raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+    else:
+        if maps is not None or out is not None:
+            raise ValueError('maps and out need min_score')
+        if return_rejected:
+            raise ValueError('return_rejected needs min_score')
+    H, W = d_row.shape
+    with _on(stream):
+        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        score = torch.empty((H, W), dtype=torch.float64, device=dev)
+        warped = torch.empty((H, W), dtype=torch.float64, device=dev) if return_warped else None
+        rejected = torch.empty((H, W), dtype=torch.uint8, device=dev) if return_rejected else None
+        M = 1
+        if min_score is not None:
+            M = 1 if maps.dim() == 2 else maps.shape[0]
+            # (the planes are read from where they are: in place they alias `out`, which the kernel allows)
+            if out is None:
+                out = maps.clone(memory_format=torch.contiguous_format)
+            elif out.data_ptr() != maps.data_ptr():
+                out.copy_(maps)
+        if H and W and M:
+            if not a.numel():
+                raise ValueError('empty image')
+            lib = L.load()
+            nbytes = lib.dm_photo_bytes(M, H, W)
+            if not nbytes:
+                raise NotImplementedError('photo_score does not take %d maps of %d x %d cells' % (M, H, W))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            L.check(lib.dm_photo_score(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
+                                       L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                       radius, L.DM_PHOTO_REJECT if min_score is not None else 0,
+                                       min_score if min_score is not None else 0.0,
+                                       L.ptr(out) if min_score is not None else L.ptr(None), M, L.ptr(score),
+                                       L.ptr(warped), L.ptr(rejected), L.ptr(work), L.stream_handle()),
+                    'dm_photo_score')
+    res = (score,) + ((out,) if min_score is not None else ()) + ((warped,) if return_warped else ()) + \
+        ((rejected,) if return_rejected else ())
+    return res if len(res) > 1 else score
+
+
+def photo_stage(img1, img2, d_map, modes, photo, offset, reject):
+    """One stage of the ``photo=`` chain on the stitched d_map [len(modes)][H][W], in place.
+    ``reject``: the rejection after the median -> (d_map, uint8 mask); else the score of the final
+    planes -> score."""
+    ir, ic = photo_planes(modes)
+    if reject:
+        _, d, rejected = photo_score(img1, img2, d_map[ir], d_map[ic], photo[0], offset=offset, min_score=photo[1],
+                                     maps=d_map, out=d_map, return_rejected=True)
+        return d, rejected
+    return photo_score(img1, img2, d_map[ir], d_map[ic], photo[0], offset=offset)

@@ -38,7 +38,8 @@ class ImageCutSolver():
         smooth=None,
         smooth_guide='image',
         median=None,
-        median_weight=None
+        median_weight=None,
+        photo=None
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -98,6 +99,16 @@ class ImageCutSolver():
         if median_weight not in (None, 'correlation'):
             raise ValueError("median_weight must be None or 'correlation'")
         self.median_weight = median_weight
+        # radius or (radius, min_score) of the photo-consistency score (engine.photo_score): img2 is
+        # resampled where d_map claims the match and correlated with img1 around the cell.  photo_map is
+        # the score of the final d_map; with min_score the cells scoring below it are also rejected
+        # (NaN in every mode) after the median and before the speckle filter, and photo_reject_map marks
+        # them.  Needs both 'elevation' and 'elevation2' in degree_map_mode.  None: nothing is scored
+        self.photo = engine.photo_params(photo) if photo is not None else None
+        if self.photo is not None:
+            engine.photo_planes(degree_map_mode)
+        self.photo_map = None
+        self.photo_reject_map = None
 
         self.log_flg = True
 
@@ -170,8 +181,14 @@ class ImageCutSolver():
         holes, self.fill is what fills); no tensor is added.  With self.median set d_map is median
         filtered first, immediately after the stitch and before the speckle filter, the fill and the
         smoothing (engine.median_filter, all modes in one call, in place, weighted by out_map when
-        self.median_weight is 'correlation'; holes stay holes); no tensor is added.  The chain is
-        stitch -> median -> speckle -> fill -> smooth."""
+        self.median_weight is 'correlation'; holes stay holes); no tensor is added.  With self.photo
+        set the final d_map is scored last (engine.photo_score against self.img1 / self.img2, map cell
+        (y, x) at pixel (y + e, x + e), e = exclusive_pix) and the float64 score [H][W] is appended
+        after every other tensor; with a min_score the cells that score below it are first rejected
+        in every mode, after the median and before the speckle filter, and the uint8 mask [H][W] of
+        those cells comes immediately before the score.  The chain is stitch -> median -> photo
+        reject -> speckle -> fill -> smooth -> photo score, the tuple (d_map, out_map[, err]
+        [, spread, count][, speckles][, holes][[, rejected], score])."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -193,7 +210,7 @@ class ImageCutSolver():
                                              merge=self.merge, merge_min_count=self.merge_min_count,
                                              speckle=self.speckle, smooth=self.smooth,
                                              smooth_guide=self.smooth_guide, median=self.median,
-                                             median_weight=self.median_weight)
+                                             median_weight=self.median_weight, photo=self.photo)
         if self.merge is not None:
             if self.consistency is not None:
                 fwd, bwd = engine.solve_tiles_bidir(*args)
@@ -212,6 +229,11 @@ class ImageCutSolver():
             d = engine.median_filter(maps[0], self.median[0], weight=engine.median_weight(self.median_weight, maps),
                                      iters=self.median[1], out=maps[0])
             maps = (d,) + tuple(maps[1:])
+        rejected = None
+        if self.photo is not None and self.photo[1] is not None:
+            d, rejected = engine.photo_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.photo,
+                                             self.exclusive_pix, True)
+            maps = (d,) + tuple(maps[1:])
         if self.speckle is not None:
             d, removed = engine.filter_speckles(maps[0], *self.speckle, out=maps[0], return_removed=True)
             maps = (d,) + tuple(maps[1:]) + (removed,)
@@ -222,6 +244,10 @@ class ImageCutSolver():
             guide = engine.smooth_guide(self.img1, self.exclusive_pix, maps[0]) if self.smooth_guide == 'image' else None
             d = engine.bilateral_filter(maps[0], *self.smooth, guide=guide, out=maps[0])
             maps = (d,) + tuple(maps[1:])
+        if self.photo is not None:
+            score = engine.photo_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.photo,
+                                       self.exclusive_pix, False)
+            maps = tuple(maps) + ((rejected,) if rejected is not None else ()) + (score,)
         return maps
 
     def _execute_matching(self):
@@ -229,6 +255,12 @@ class ImageCutSolver():
         小画像ごとにマッチングを行い結果を結合
         """
         maps = self._execute_matching_device()
+        if self.photo is not None:         # the last tensors: taken off first, the indices below stay as they were
+            self.photo_map = maps[-1].cpu().numpy() if maps[-1] is not None else None
+            maps = maps[:-1]
+            if self.photo[1] is not None:  # the cells rejected for scoring below min_score (before any fill)
+                self.photo_reject_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
+                maps = maps[:-1]
         d_map, out_map = maps[0], maps[1]
         # (None on the ranks other than 0 of a sharded solve with tile_sharding(result='root'))
         self.d_map = d_map.cpu().numpy() if d_map is not None else None

@@ -385,7 +385,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
                         merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
                         smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
-                        medianer=None):
+                        medianer=None, photo=None, photoer=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -424,9 +424,23 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     modes in one call (engine.median_filter, or ``medianer(d_map, weight or None, radius, iters) ->
     d_map``).  ``median_weight``: None -- the unweighted median -- or 'correlation' -- weighted by
     the stitched out_map, shared by all modes.  Holes stay holes; no tensor is added.  None:
-    nothing changes.  The chain is stitch -> median -> speckle -> fill -> smooth."""
+    nothing changes.
+    ``photo``: a radius or (radius, min_score), with both 'elevation' and 'elevation2' in ``modes``
+    (else ValueError); rank 0 then scores the final d_map last, after the smoothing
+    (engine.photo_score against img1 / img2 with the offset e, or ``photoer(img1, img2, d_row, d_col,
+    radius, e, None, None) -> score``) and the float64 score [H][W] is appended after every other
+    tensor.  With a min_score rank 0 first rejects the cells that score below it in every mode,
+    after the median and before the speckle filter (``photoer(img1, img2, d_row, d_col, radius, e,
+    min_score, d_map) -> (score, d_map, uint8 mask)``), and the uint8 mask [H][W] comes immediately
+    before the score: (d_map, out_map[, err][, spread, count][, speckles][, holes][[, rejected],
+    score]).  None: nothing changes.  The chain is stitch -> median -> photo reject -> speckle ->
+    fill -> smooth -> photo score."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
+    pho = engine.photo_params(photo) if photo is not None else None
+    if pho is not None:
+        pho_row, pho_col = engine.photo_planes(modes)
+    pho_img1, pho_img2 = img1, img2      # (consistency stacks the pair below)
     med = engine.median_params(median) if median is not None else None
     if median_weight not in (None, 'correlation'):
         raise ValueError("median_weight must be None or 'correlation'")
@@ -471,6 +485,15 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
         else:
             d = engine.median_filter(maps[0], med[0], weight=weight, iters=med[1], out=maps[0])
         maps = (d,) + tuple(maps[1:])
+    pho_e = (window_size - 1) // 2
+    rejected = None
+    if pho is not None and pho[1] is not None and maps is not None:
+        if photoer is not None:
+            _, d, rejected = photoer(pho_img1, pho_img2, maps[0][pho_row], maps[0][pho_col], pho[0], pho_e, pho[1],
+                                     maps[0])
+        else:
+            d, rejected = engine.photo_stage(pho_img1, pho_img2, maps[0], modes, pho, pho_e, True)
+        maps = (d,) + tuple(maps[1:])
     if spk is not None:
         nmaps += 1
         if maps is not None:
@@ -497,6 +520,14 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             guide = engine.smooth_guide(guide_img, e, maps[0]) if smooth_guide == 'image' else None
             d = engine.bilateral_filter(maps[0], *smo, guide=guide, out=maps[0])
         maps = (d,) + tuple(maps[1:])
+    if pho is not None:
+        nmaps += 1 if pho[1] is None else 2
+        if maps is not None:
+            if photoer is not None:
+                score = photoer(pho_img1, pho_img2, maps[0][pho_row], maps[0][pho_col], pho[0], pho_e, None, None)
+            else:
+                score = engine.photo_stage(pho_img1, pho_img2, maps[0], modes, pho, pho_e, False)
+            maps = tuple(maps) + ((rejected,) if pho[1] is not None else ()) + (score,)
     if not _group() or world()[1] == 1:
         return maps
     if result == 'root':
@@ -514,6 +545,10 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
         if iters is not None:
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
+        if pho is not None:
+            if pho[1] is not None:
+                out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
+            out.append(torch.empty((H, W), dtype=torch.float64, device=dev))
     else:
         out = [torch.as_tensor(m) for m in maps]
     for t in out:

@@ -490,6 +490,78 @@ int dm_median_filter(const double *d_in, const double *d_weight /* may be NULL *
                      int32_t flags, double *d_out, uint8_t *d_changed /* may be NULL */,
                      void *d_work, void *stream);
 
+/* ---- Photo-consistency score (dm_photo.hip) -----------------------------------------------
+ * Not in the reference.  out_map is the matcher's score of the correspondence it found: its
+ * level 0 is normalised per patch, and the median, the fill and the smoothing move cells without
+ * updating it.  dm_photo_score judges any map, however it was produced: it resamples img2 at
+ * the position the map claims for a cell and correlates it with img1 around the cell (zero-mean
+ * normalised cross-correlation, in [-1, 1]).
+ *   images   img1, img2: uint8 [Hi][Wi], rows stride1 / stride2 bytes apart (>= Wi)
+ *   planes   d_row, d_col: float64 [H][W], the 'elevation2' and 'elevation' maps: elevation =
+ *            j - match_col, elevation2 = i - match_row (Calc_difference.cal_map), so the match of
+ *            a cell lies at its own position minus the disparity
+ *   offsets  map cell (y, x) is image pixel (cy, cx) = (y + oy, x + ox)
+ *   window   radius r, 1 <= r <= 7, n = (2r + 1)^2
+ * Per cell:
+ *   1. d_row or d_col not finite (the range test on the double: NaN and +-inf fail): the cell
+ *      is unscored and has no warped value.
+ *   2. py = (double)cy - d_row, px = (double)cx - d_col.  The tests of 3 and 6 are made on py and
+ *      px in double; only a position that passed them is converted: iy = floor(py), ix =
+ *      floor(px), fy = py - iy, fx = px - ix (exact, in [0, 1)).
+ *   3. The cell is unscored unless the img1 window, rows cy-r .. cy+r and columns cx-r .. cx+r,
+ *      and the img2 patch, rows iy-r .. iy+r+1 and columns ix-r .. ix+r+1, lie inside the image:
+ *      r <= py < Hi - r - 1 and r <= px < Wi - r - 1.  The extra row and column are required
+ *      even when fy or fx is 0: one rule, no special case.
+ *   4. A is the img1 window, P0, P1, P2, P3 the (2r+1)^2 windows of img2 whose top-left corners
+ *      are (iy-r, ix-r) + (0,0), (0,1), (1,0), (1,1).  As exact integers (sums over the window's
+ *      n taps):
+ *        sa = sum A, saa = sum A^2, S_k = sum P_k,
+ *        CA_k = n sum(A P_k) - sa S_k,   CB_kl = n sum(P_k P_l) - S_k S_l (k <= l),
+ *        VA = n saa - sa^2
+ *      (n sum(P_k P_l) reaches 3.29e9 at r = 7: 64-bit arithmetic).  Each is below 2^53 in
+ *      magnitude and converts to double exactly.
+ *   5. In float64, one rounding per operation, no contraction:
+ *        w0 = (1-fy) * (1-fx), w1 = (1-fy) * fx, w2 = fy * (1-fx), w3 = fy * fx
+ *        num = ((w0 CA_0 + w1 CA_1) + w2 CA_2) + w3 CA_3
+ *        vb  = the sum, left to right, over k <= l (k outer, l inner: 00 01 02 03 11 12 13 22 23
+ *              33) of (c * (w_k * w_l)) * CB_kl, c = 1 for k = l, else 2
+ *        score = 0.0 unless VA > 0 and vb > 0; else t = num / sqrt(VA * vb), and the score is
+ *                1.0 if t > 1, -1.0 if t < -1, else t
+ *   6. warped (optional) = ((w0 q00 + w1 q01) + w2 q10) + w3 q11 with q the img2 pixels at
+ *      (iy, ix), (iy, ix+1), (iy+1, ix), (iy+1, ix+1), whenever those four lie inside the image
+ *      (0 <= py < Hi - 1 and 0 <= px < Wi - 1), whatever rule 3 says; else NaN.
+ *   7. An unscored cell has the score NaN (0x7ff8000000000000).
+ * Rejection (DM_PHOTO_REJECT, threshold min_score in [-1, 1]): in every one of the M planes of
+ * d_maps [M][H][W] a cell whose score is not NaN and is below min_score becomes NaN
+ * (0x7ff8000000000000); every other cell, the unscored ones included, keeps its bits.
+ * d_rejected (uint8 [H][W]) receives 1 at exactly those cells, else 0.  A cell reads only its
+ * own d_row / d_col and they are read before d_maps is written, so d_row and d_col may be
+ * planes of d_maps.
+ * It follows that with integer disparities and identical windows the score is exactly 1.0
+ * (sqrt(x * x) = x), that a flat window on either side gives exactly 0.0, and that the result
+ * does not depend on the order of summation: every sum is an integer.
+ * tests/test_photo_host.py restates this in plain loops; the kernel equals it bit for bit. */
+enum { DM_PHOTO_REJECT = 1 };
+
+/* Bytes of the workspace dm_photo_score asks for (it needs none: a constant 16); 0 for a shape
+ * it does not take (dm_median_bytes' limits). */
+size_t dm_photo_bytes(int32_t M, int32_t H, int32_t W);
+
+/* d_score, d_warped (float64 [H][W]) and d_rejected may be NULL.  Without DM_PHOTO_REJECT
+ * d_maps, M and min_score are not read, d_rejected must be NULL and one of d_score / d_warped
+ * must be given.  d_work: dm_photo_bytes(M, H, W) bytes, not NULL.  DM_ERR_ARG for a null
+ * image / plane / workspace, a side below 1, a stride below Wi, an offset outside
+ * [-2^30, 2^30], a radius outside [1, 7], unknown flag bits, with DM_PHOTO_REJECT a null
+ * d_maps, M < 1 or a min_score outside [-1, 1] (NaN included); DM_ERR_UNSUPPORTED for the
+ * other shapes dm_photo_bytes refuses.  Validation precedes every HIP call; nothing is
+ * allocated, nothing synchronises, one launch on `stream`. */
+int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2, int64_t stride2,
+                   int32_t Hi, int32_t Wi, const double *d_row, const double *d_col, int32_t H, int32_t W,
+                   int32_t oy, int32_t ox, int32_t radius, int32_t flags, double min_score,
+                   double *d_maps /* may be NULL */, int32_t M, double *d_score /* may be NULL */,
+                   double *d_warped /* may be NULL */, uint8_t *d_rejected /* may be NULL */,
+                   void *d_work, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -572,8 +644,8 @@ const char *dm_last_error(void);
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
- * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16 and
- * dm_level_num_f16 are additive entries within 1.10:
+ * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16,
+ * dm_level_num_f16, dm_photo_bytes and dm_photo_score are additive entries within 1.10:
  * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);
 

@@ -32,6 +32,7 @@ DM_MERGE_MAX_CAND = 64   # tiles over one pixel that dm_stitch_merge takes
 DM_BILAT_FILL, DM_BILAT_GUIDE_U8 = 1, 2   # dm_bilateral_filter flags
 DM_MEDIAN_FILL = 1   # dm_median_filter flag
 DM_PHOTO_REJECT = 1   # dm_photo_score flag
+DM_REFINE_SUBPIX = 1   # dm_photo_refine flag
 
 
 class DmUnavailable(ImportError):
@@ -104,6 +105,9 @@ SIGNATURES = {
     'dm_photo_bytes': ([_I, _I, _I], ctypes.c_size_t),
     'dm_photo_score': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
                         ctypes.c_double, _P, _I, _P, _P, _P, _P, _P], ctypes.c_int),
+    'dm_photo_refine_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_size_t),
+    'dm_photo_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
+                         ctypes.c_double, _I, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
 }
 
 _lib = None

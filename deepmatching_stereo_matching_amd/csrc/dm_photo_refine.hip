@@ -1,0 +1,358 @@
+// dm_photo_refine.hip -- gfx950 kernel + C ABI of the local re-matching of a disparity map
+// (dm_photo_refine, include/dmstereo.h): every cell scores the (2s+1)^2 integer neighbours of the
+// position its disparity claims with dm_photo_score's ZNCC and moves to the best one, optionally
+// with a parabola through the winner's neighbours per axis.
+//
+// k_refine<ND, S>: one launch, one thread per cell, workgroups of 32 x 8 cells.  A candidate
+// (dy, dx) needs the four img2 windows Q[dy + {0,1}][dx + {0,1}]; the candidates of one row dy
+// share the two rows of windows Q[dy][.] and Q[dy + 1][.], K = 2S + 2 column shifts each.  So a
+// thread makes one walk per candidate row: the 2r+2 image rows iy+dy-r .. iy+dy+r+1, each read
+// once as unaligned dwords (dm_photo.h) from the first column any scored candidate needs to the
+// last, and cut into the K shifted rows W[0 .. K) by funnel shifts.  Per image row and shift the
+// walk adds, as chains of v_dot4_u32_u8, W.1, W.W, W[j].W[j+1] and a.W for the upper and for the
+// lower window, and against the row above P[j].W[j], P[j].W[j+1], P[j+1].W[j]: 9 K - 4 chains
+// where 2S+1 separate dm_photo_score walks make 20 (2S+1).  The twenty sums of candidate j of the
+// row are then a selection of these, and the float64 tail is dm_photo_score's, operation for
+// operation, so candidate (0, 0) has that entry's bits.  sum A and sum A^2 are taken once.
+//
+// Every sum stays below 225 * 255^2 < 2^24; the products with n and of two sums are int64.  The
+// candidate rows and columns are clamped to the scored ones before anything is read, so no byte
+// outside the image rows is touched: the first column read is ix+dxlo-r >= 0, the last
+// ix+dxhi+r+1 <= Wi-1, and the tail dword ends with the last byte (at least 4 bytes are read:
+// 2r+2 >= 4).  The (2S+1)^2 scores of a cell live in a per-thread array; the winner is found by
+// one ordered scan, so the result does not depend on anything but the cell.  A cell reads only
+// its own d_row / d_col and does so before it writes, so the outputs may alias the inputs.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdarg.h>
+#include <stdint.h>
+#include <string.h>
+
+#include "../../include/dmstereo.h"
+#include "dm_photo.h"
+
+// error reporting lives in dm_kernels.hip (one thread-local message per thread)
+__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
+
+static int rfail(int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    const int r = dm_vfail(code, fmt, ap);
+    va_end(ap);
+    return r;
+}
+
+#define REF_SMAX 3
+#define REF_POSMAX 1073741824.0      // 2^30
+
+// the first nbytes (4 .. 4 NW) bytes at p as NW little-endian dwords, zero from nbytes on.  Reads
+// nothing outside [p, p + nbytes).
+template <int NW>
+__device__ __forceinline__ void ref_row(const uint8_t *p, int nbytes, uint32_t (&d)[NW])
+{
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+        const int left = nbytes - 4 * k;      // bytes of the row from dword k on
+        if (left >= 4)
+            d[k] = pho_ld4(p + 4 * k);
+        else if (left > 0)
+            d[k] = pho_ld4(p + nbytes - 4) >> (8 * (4 - left));
+        else
+            d[k] = 0u;
+    }
+}
+
+// dm_photo_score's rule 5 on the exact sums of one candidate (include/dmstereo.h)
+__device__ __forceinline__ double ref_tail(int64_t n, int64_t Sa, double VA, double w0, double w1, double w2, double w3,
+                                           uint32_t S0, uint32_t S1, uint32_t S2, uint32_t S3, uint32_t A0, uint32_t A1,
+                                           uint32_t A2, uint32_t A3, uint32_t B00, uint32_t B01, uint32_t B02,
+                                           uint32_t B03, uint32_t B11, uint32_t B12, uint32_t B13, uint32_t B22,
+                                           uint32_t B23, uint32_t B33)
+{
+    const int64_t s0 = S0, s1 = S1, s2 = S2, s3 = S3;
+    const double CA0 = (double)(n * (int64_t)A0 - Sa * s0), CA1 = (double)(n * (int64_t)A1 - Sa * s1);
+    const double CA2 = (double)(n * (int64_t)A2 - Sa * s2), CA3 = (double)(n * (int64_t)A3 - Sa * s3);
+    const double C00 = (double)(n * (int64_t)B00 - s0 * s0), C01 = (double)(n * (int64_t)B01 - s0 * s1);
+    const double C02 = (double)(n * (int64_t)B02 - s0 * s2), C03 = (double)(n * (int64_t)B03 - s0 * s3);
+    const double C11 = (double)(n * (int64_t)B11 - s1 * s1), C12 = (double)(n * (int64_t)B12 - s1 * s2);
+    const double C13 = (double)(n * (int64_t)B13 - s1 * s3), C22 = (double)(n * (int64_t)B22 - s2 * s2);
+    const double C23 = (double)(n * (int64_t)B23 - s2 * s3), C33 = (double)(n * (int64_t)B33 - s3 * s3);
+    const double num = ((w0 * CA0 + w1 * CA1) + w2 * CA2) + w3 * CA3;
+    double vb = (1.0 * (w0 * w0)) * C00;
+    vb = vb + (2.0 * (w0 * w1)) * C01;
+    vb = vb + (2.0 * (w0 * w2)) * C02;
+    vb = vb + (2.0 * (w0 * w3)) * C03;
+    vb = vb + (1.0 * (w1 * w1)) * C11;
+    vb = vb + (2.0 * (w1 * w2)) * C12;
+    vb = vb + (2.0 * (w1 * w3)) * C13;
+    vb = vb + (1.0 * (w2 * w2)) * C22;
+    vb = vb + (2.0 * (w2 * w3)) * C23;
+    vb = vb + (1.0 * (w3 * w3)) * C33;
+    if (VA > 0.0 && vb > 0.0) {
+        const double t = num / sqrt(VA * vb);
+        return t > 1.0 ? 1.0 : (t < -1.0 ? -1.0 : t);
+    }
+    return 0.0;
+}
+
+// the parabola through (-1, sm), (0, s0), (1, sp): its peak, clamped to [-0.5, 0.5]; 0 unless it opens downwards
+__device__ __forceinline__ double ref_peak(double sm, double s0, double sp)
+{
+    const double den = (sm + sp) - 2.0 * s0;
+    if (!(den < 0.0)) return 0.0;
+    const double t = (0.5 * (sm - sp)) / den;
+    return t > 0.5 ? 0.5 : (t < -0.5 ? -0.5 : t);
+}
+
+// grid: tiles_x * tiles_y workgroups of PHO_TX x PHO_TY cells.  ND = (r + 2) / 2 dwords per window row,
+// S the search radius.
+template <int ND, int S>
+__global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, size_t stride1, const uint8_t *img2,
+                                                          size_t stride2, int Hi, int Wi, const double *d_row,
+                                                          const double *d_col, int H, int W, int tiles_x, int oy,
+                                                          int ox, int r, double min_gain, int subpix,
+                                                          const uint8_t *mask, double *out_row, double *out_col,
+                                                          double *score, int8_t *shift)
+{
+    constexpr int NC = 2 * S + 1;                  // candidates a side
+    constexpr int K = 2 * S + 2;                   // window shifts a side
+    constexpr int NW = ND + (2 * S + 3) / 4;       // dwords of the widest row read: 4 ND + 2 S bytes
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
+    if (y >= H || x >= W) return;
+    const size_t c = (size_t)y * W + x;
+    const double dr = d_row[c], dc = d_col[c];
+    const double NaN = __longlong_as_double(0x7ff8000000000000LL);
+    double o_row = dr, o_col = dc, o_score = NaN;
+    int o_dy = 0, o_dx = 0;
+    const int cy = y + oy, cx = x + ox;
+    bool live = (!mask || mask[c] != 0) && pho_finite(dr) && pho_finite(dc) && cy >= r && cy <= Hi - 1 - r &&
+                cx >= r && cx <= Wi - 1 - r;
+    double py = 0.0, px = 0.0;
+    if (live) {
+        py = (double)cy - dr, px = (double)cx - dc;
+        // the test is made in double: only a position it passed is converted
+        live = py >= -REF_POSMAX && py <= REF_POSMAX && px >= -REF_POSMAX && px <= REF_POSMAX;
+    }
+    if (live) {
+        const double fly = floor(py), flx = floor(px);
+        const int iy = (int)fly, ix = (int)flx;      // |iy|, |ix| <= 2^30
+        const double fy = py - fly, fx = px - flx;
+        const double gy = 1.0 - fy, gx = 1.0 - fx;
+        const double w0 = gy * gx, w1 = gy * fx, w2 = fy * gx, w3 = fy * fx;
+        // the scored candidates: r <= iy + dy <= Hi - r - 2, r <= ix + dx <= Wi - r - 2 (no overflow: Hi, Wi <= 2^30)
+        const int dylo = max(-S, r - iy), dyhi = min(S, Hi - r - 2 - iy);
+        const int dxlo = max(-S, r - ix), dxhi = min(S, Wi - r - 2 - ix);
+        double sc[NC * NC];
+#pragma unroll
+        for (int k = 0; k < NC * NC; ++k) sc[k] = NaN;
+        if (dylo <= dyhi && dxlo <= dxhi) {
+            const int D = 2 * r + 1;
+            const int64_t n = (int64_t)D * D;
+            const int ncand = dxhi - dxlo + 1;           // candidates of a row: 1 .. NC
+            const int nbytes = ncand + D;                // bytes of an image row that they need: >= 4
+            uint32_t wmask[ND];      // the bytes 0 .. 2r of a window row
+#pragma unroll
+            for (int k = 0; k < ND; ++k) {
+                const int nb = D - 4 * k;      // bytes of the window in dword k: >= 1
+                wmask[k] = nb >= 4 ? 0xffffffffu : (0xffffffffu >> (8 * (4 - nb)));
+            }
+            const uint8_t *pa = img1 + (size_t)(cy - r) * stride1 + (cx - r);
+            uint32_t sa = 0, saa = 0;
+            for (int q = 0; q < D; ++q) {
+                uint32_t ac[ND];
+                pho_row<ND>(pa + (size_t)q * stride1, D, ac);
+#pragma unroll
+                for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
+                sa = pho_sum<ND>(ac, sa);
+                saa = pho_dot<ND>(ac, ac, saa);
+            }
+            const int64_t Sa = sa;
+            const double VA = (double)(n * (int64_t)saa - Sa * Sa);
+            for (int dy = dylo; dy <= dyhi; ++dy) {
+                const uint8_t *pb = img2 + (size_t)(iy + dy - r) * stride2 + (ix + dxlo - r);
+                uint32_t St[K], Sb[K], Qt[K], Qb[K], At[K], Ab[K], Dn[K];      // per window: sums, squares, a., the window below
+                uint32_t Et[K - 1], Eb[K - 1], Ds[K - 1], Dw[K - 1];           // per pair: ->, -> below, down-right, down-left
+                uint32_t Pw[K][ND], ap[ND];                                    // the row above
+#pragma unroll
+                for (int j = 0; j < K; ++j) {
+                    St[j] = Sb[j] = Qt[j] = Qb[j] = At[j] = Ab[j] = Dn[j] = 0;
+#pragma unroll
+                    for (int k = 0; k < ND; ++k) Pw[j][k] = 0;
+                }
+#pragma unroll
+                for (int j = 0; j < K - 1; ++j) Et[j] = Eb[j] = Ds[j] = Dw[j] = 0;
+#pragma unroll
+                for (int k = 0; k < ND; ++k) ap[k] = 0;
+                for (int q = 0; q <= D; ++q) {
+                    uint32_t raw[NW], Wc[K][ND], ac[ND];
+                    ref_row<NW>(pb + (size_t)q * stride2, nbytes, raw);
+#pragma unroll
+                    for (int j = 0; j < K; ++j) {
+#pragma unroll
+                        for (int k = 0; k < ND; ++k) {
+                            const int b = j + 4 * k, qd = b >> 2, rm = b & 3;      // compile-time after unrolling
+                            const uint32_t lo = qd < NW ? raw[qd < NW ? qd : 0] : 0u;
+                            const uint32_t hi = qd + 1 < NW ? raw[qd + 1 < NW ? qd + 1 : 0] : 0u;
+                            const uint32_t v = rm ? ((lo >> (8 * rm)) | (hi << (32 - 8 * rm))) : lo;
+                            Wc[j][k] = v & wmask[k];
+                        }
+                    }
+                    if (q < D) {      // a row of the upper windows, and of the img1 window
+                        pho_row<ND>(pa + (size_t)q * stride1, D, ac);
+#pragma unroll
+                        for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
+#pragma unroll
+                        for (int j = 0; j < K; ++j) {
+                            St[j] = pho_sum<ND>(Wc[j], St[j]);
+                            Qt[j] = pho_dot<ND>(Wc[j], Wc[j], Qt[j]);
+                            At[j] = pho_dot<ND>(ac, Wc[j], At[j]);
+                        }
+#pragma unroll
+                        for (int j = 0; j < K - 1; ++j) Et[j] = pho_dot<ND>(Wc[j], Wc[j + 1], Et[j]);
+                    }
+                    if (q > 0) {      // a row of the lower windows: it meets row q - 1 of the upper ones and of the img1 window
+#pragma unroll
+                        for (int j = 0; j < K; ++j) {
+                            Sb[j] = pho_sum<ND>(Wc[j], Sb[j]);
+                            Qb[j] = pho_dot<ND>(Wc[j], Wc[j], Qb[j]);
+                            Ab[j] = pho_dot<ND>(ap, Wc[j], Ab[j]);
+                            Dn[j] = pho_dot<ND>(Pw[j], Wc[j], Dn[j]);
+                        }
+#pragma unroll
+                        for (int j = 0; j < K - 1; ++j) {
+                            Eb[j] = pho_dot<ND>(Wc[j], Wc[j + 1], Eb[j]);
+                            Ds[j] = pho_dot<ND>(Pw[j], Wc[j + 1], Ds[j]);
+                            Dw[j] = pho_dot<ND>(Pw[j + 1], Wc[j], Dw[j]);
+                        }
+                    }
+#pragma unroll
+                    for (int j = 0; j < K; ++j)
+#pragma unroll
+                        for (int k = 0; k < ND; ++k) Pw[j][k] = Wc[j][k];
+                    if (q < D) {
+#pragma unroll
+                        for (int k = 0; k < ND; ++k) ap[k] = ac[k];
+                    }
+                }
+                // candidate j of this row: P0 = upper j, P1 = upper j+1, P2 = lower j, P3 = lower j+1
+#pragma unroll
+                for (int j = 0; j < NC; ++j) {
+                    if (j < ncand)
+                        sc[(dy + S) * NC + (dxlo + S + j)] =
+                            ref_tail(n, Sa, VA, w0, w1, w2, w3, St[j], St[j + 1], Sb[j], Sb[j + 1], At[j], At[j + 1],
+                                     Ab[j], Ab[j + 1], Qt[j], Et[j], Dn[j], Ds[j], Qt[j + 1], Dw[j], Dn[j + 1], Qb[j],
+                                     Eb[j], Qb[j + 1]);
+                }
+            }
+            // the winner: the highest score; ties to the smallest dy^2 + dx^2, then the smaller dy, then the smaller dx
+            // (the scan runs dy, then dx upwards, so among equal scores and distances the first one met stays)
+            double best = NaN;
+            int bdy = 0, bdx = 0, bd2 = 0;
+            bool any = false;
+            for (int k = 0; k < NC * NC; ++k) {
+                const double s = sc[k];
+                if (s != s) continue;
+                const int dy = k / NC - S, dx = k % NC - S, d2 = dy * dy + dx * dx;
+                if (!any || s > best || (s == best && d2 < bd2)) best = s, bdy = dy, bdx = dx, bd2 = d2, any = true;
+            }
+            if (any) {
+                const double centre = sc[S * NC + S];
+                if (centre == centre && !(best > centre + min_gain)) best = centre, bdy = 0, bdx = 0;
+                o_score = best, o_dy = bdy, o_dx = bdx;
+                if (bdy != 0 || bdx != 0) {
+                    double ty = 0.0, tx = 0.0;
+                    if (subpix) {
+                        const int k = (bdy + S) * NC + (bdx + S);
+                        if (bdy > -S && bdy < S) {
+                            const double sm = sc[k - NC], sp = sc[k + NC];
+                            if (sm == sm && sp == sp) ty = ref_peak(sm, best, sp);
+                        }
+                        if (bdx > -S && bdx < S) {
+                            const double sm = sc[k - 1], sp = sc[k + 1];
+                            if (sm == sm && sp == sp) tx = ref_peak(sm, best, sp);
+                        }
+                    }
+                    o_row = dr - ((double)bdy + ty);
+                    o_col = dc - ((double)bdx + tx);
+                }
+            }
+        }
+    }
+    out_row[c] = o_row;
+    out_col[c] = o_col;
+    if (score) score[c] = o_score;
+    if (shift) {
+        shift[c] = (int8_t)o_dy;
+        shift[(size_t)H * W + c] = (int8_t)o_dx;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------
+// false for a shape the entry does not take (dm_photo_bytes' limits, and images of at most 2^30 a side)
+static bool ref_plan(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t search)
+{
+    if (radius < 1 || radius > PHO_RMAX || search < 1 || search > REF_SMAX) return false;
+    if (Hi < 1 || Wi < 1 || Hi > (1 << 30) || Wi > (1 << 30)) return false;
+    return dm_photo_bytes(1, H, W) != 0;
+}
+
+extern "C" {
+
+size_t dm_photo_refine_bytes(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t search)
+{
+    return ref_plan(Hi, Wi, H, W, radius, search) ? 16 : 0;
+}
+
+int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2, int64_t stride2, int32_t Hi,
+                    int32_t Wi, const double *d_row, const double *d_col, int32_t H, int32_t W, int32_t oy, int32_t ox,
+                    int32_t radius, int32_t search, double min_gain, int32_t flags, const uint8_t *d_mask,
+                    double *d_out_row, double *d_out_col, double *d_score, int8_t *d_shift, void *d_work, void *stream)
+{
+    if (!d_img1 || !d_img2 || !d_row || !d_col || !d_out_row || !d_out_col || !d_work)
+        return rfail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
+    if (Hi < 1 || Wi < 1) return rfail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
+    if (stride1 < Wi || stride2 < Wi)
+        return rfail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
+                     (long long)stride2);
+    if (H < 1 || W < 1) return rfail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
+    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
+        return rfail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
+    if (radius < 1 || radius > PHO_RMAX) return rfail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (search < 1 || search > REF_SMAX) return rfail(DM_ERR_ARG, "search must be in [1, %d] (got %d)", REF_SMAX, search);
+    if (!(min_gain >= 0.0 && min_gain <= 2.0)) return rfail(DM_ERR_ARG, "min_gain must be in [0, 2] (got %g)", min_gain);
+    if (flags & ~DM_REFINE_SUBPIX) return rfail(DM_ERR_ARG, "unknown flags 0x%x", flags);
+    if (!ref_plan(Hi, Wi, H, W, radius, search))
+        return rfail(DM_ERR_UNSUPPORTED,
+                     "photo refine of %d x %d cells on a %d x %d image (at most 2^31 - 1 cells, 2^30 pixels a side)", H,
+                     W, Hi, Wi);
+    const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
+    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
+    hipStream_t st = (hipStream_t)stream;
+    const int subpix = (flags & DM_REFINE_SUBPIX) ? 1 : 0;
+#define REF_GO(ND_, S_)                                                                                               \
+    k_refine<ND_, S_><<<grid, PHO_TX * PHO_TY, 0, st>>>(d_img1, (size_t)stride1, d_img2, (size_t)stride2, Hi, Wi, d_row, \
+                                                        d_col, H, W, tiles_x, oy, ox, radius, min_gain, subpix, d_mask, \
+                                                        d_out_row, d_out_col, d_score, d_shift)
+#define REF_GO_S(ND_)                                                                                                 \
+    switch (search) {                                                                                                 \
+    case 1: REF_GO(ND_, 1); break;                                                                                    \
+    case 2: REF_GO(ND_, 2); break;                                                                                    \
+    default: REF_GO(ND_, 3); break;                                                                                   \
+    }
+    switch ((radius + 2) / 2) {
+    case 1: REF_GO_S(1); break;
+    case 2: REF_GO_S(2); break;
+    case 3: REF_GO_S(3); break;
+    default: REF_GO_S(4); break;
+    }
+#undef REF_GO_S
+#undef REF_GO
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return rfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e), (int)e);
+    return DM_OK;
+}
+
+} // extern "C"

@@ -1106,3 +1106,124 @@ def photo_stage(img1, img2, d_map, modes, photo, offset, reject):
                                      maps=d_map, out=d_map, return_rejected=True)
         return d, rejected
     return photo_score(img1, img2, d_map[ir], d_map[ic], photo[0], offset=offset)
+
+
+def refine_params(refine):
+    """The ``refine=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius, search,
+    min_gain): ``(radius, search)`` or ``(radius, search, min_gain)`` with an int radius in [1, 7]
+    (the window is (2 radius + 1)^2 pixels), an int search in [1, 3] (the candidates are the
+    (2 search + 1)^2 integer neighbours) and min_gain a real in [0, 2] (0.0 in the first form): a
+    neighbour replaces the cell's own position only if it scores more than min_gain higher."""
+    if not isinstance(refine, (tuple, list)) or len(refine) not in (2, 3):
+        raise ValueError('refine must be (radius, search), (radius, search, min_gain) or None')
+    radius, search = refine[0], refine[1]
+    min_gain = refine[2] if len(refine) == 3 else 0.0
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
+        raise ValueError('refine radius must be an int in [1, 7] (got %r)' % (radius,))
+    if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 1 <= int(search) <= 3:
+        raise ValueError('refine search must be an int in [1, 3] (got %r)' % (search,))
+    if isinstance(min_gain, bool) or not isinstance(min_gain, (int, float, np.integer, np.floating)) or \
+            not 0.0 <= float(min_gain) <= 2.0:
+        raise ValueError('refine min_gain must be a real in [0, 2] (got %r)' % (min_gain,))
+    return int(radius), int(search), float(min_gain)
+
+
+def refine_planes(modes):
+    """photo_planes for ``refine=``: the indices (row, column) of 'elevation2' and 'elevation';
+    ValueError when one is missing, or when 'distance' is asked for: a refined cell would make
+    that plane stale."""
+    if 'distance' in list(modes):
+        raise ValueError("refine does not take 'distance' in degree_map_mode: a refined cell would make it stale "
+                         '(got %r)' % (list(modes),))
+    return photo_planes(modes)
+
+
+def refine_where(where, fill):
+    """The ``refine_where=`` keyword: 'filled' (only the cells the fill produced; needs ``fill=``) or
+    'all'."""
+    if where not in ('filled', 'all'):
+        raise ValueError("refine_where must be 'filled' or 'all'")
+    if where == 'filled' and fill is None:
+        raise ValueError("refine_where='filled' needs fill=")
+    return where
+
+
+def photo_refine(img1, img2, d_row, d_col, radius, search, offset=0, min_gain=0.0, subpix=True, mask=None,
+                 out=None, return_score=False, return_shift=False, stream=None):
+    """Local re-matching of a disparity map (dm_photo_refine).  Images, planes, ``offset`` and
+    ``radius`` as in photo_score.  Every cell scores the (2 search + 1)^2 integer neighbours of
+    the position its disparity claims, search in [1, 3], with photo_score's correlation and moves
+    to the best one (ties: the nearest, then the smaller dy, then the smaller dx) if that scores
+    more than ``min_gain`` (a real in [0, 2]) above its own position; with ``subpix`` a parabola
+    through the winner's scored neighbours refines each axis by at most half a pixel.  A cell
+    whose own position wins, a cell that is not finite, whose img1 window leaves the image or
+    that has no scored candidate keeps its bits.  ``mask``: a uint8 or bool tensor [H][W] on the
+    planes' device; only the cells where it is not 0 are refined.  ``out``: a pair of contiguous
+    float64 tensors [H][W] for the two planes (``out=(d_row, d_col)`` works in place when they are
+    contiguous), else new tensors.
+    -> (d_row', d_col'); then, when asked for, the float64 score of the position kept (NaN for a
+    skipped cell) and the int8 shift [2][H][W] (dy, dx) are appended."""
+    for name, d in (('d_row', d_row), ('d_col', d_col)):
+        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.float64 and d.dim() == 2):
+            raise ValueError('%s must be a 2-D float64 device (cuda) tensor' % name)
+    if d_row.shape != d_col.shape or d_row.device != d_col.device:
+        raise ValueError('d_row and d_col must have one shape and device')
+    dev = d_row.device
+    radius, search, min_gain = refine_params((radius, search, min_gain))
+    if isinstance(offset, (tuple, list)):
+        if len(offset) != 2:
+            raise ValueError('offset must be an int or (oy, ox)')
+        oy, ox = offset
+    else:
+        oy = ox = offset
+    for o in (oy, ox):
+        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not -2 ** 30 <= int(o) <= 2 ** 30:
+            raise ValueError('offset must be an int or (oy, ox) in [-2^30, 2^30] (got %r)' % (offset,))
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
+                mask.shape == d_row.shape):
+            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
+                o.shape == d_row.shape and o.is_contiguous() for o in out)):
+            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
+    H, W = d_row.shape
+    with _on(stream):
+        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
+                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
+        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
+        shift = torch.empty((2, H, W), dtype=torch.int8, device=dev) if return_shift else None
+        if H and W:
+            if not a.numel():
+                raise ValueError('empty image')
+            lib = L.load()
+            nbytes = lib.dm_photo_refine_bytes(a.shape[0], a.shape[1], H, W, radius, search)
+            if not nbytes:
+                raise NotImplementedError('photo_refine does not take %d x %d cells on a %d x %d image' %
+                                          (H, W, a.shape[0], a.shape[1]))
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            m = None if mask is None else mask.to(torch.uint8).contiguous()
+            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
+            L.check(lib.dm_photo_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
+                                        L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                        radius, search, min_gain, L.DM_REFINE_SUBPIX if subpix else 0, L.ptr(m),
+                                        L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
+                                        L.stream_handle()), 'dm_photo_refine')
+    return (o_row, o_col) + ((score,) if return_score else ()) + ((shift,) if return_shift else ())
+
+
+def refine_stage(img1, img2, d_map, modes, refine, offset, holes=None):
+    """The ``refine=`` stage of the chain on the stitched d_map [len(modes)][H][W], in place, after
+    the fill and before the smoothing.  ``holes``: the fill's uint8 mask [len(modes)][H][W] --
+    only the cells that were filled in the row or in the column plane are refined
+    (refine_where='filled') -- or None: every cell.  -> (d_map, score, int8 shift [2][H][W])."""
+    ir, ic = refine_planes(modes)
+    mask = None if holes is None else (holes[ir] | holes[ic])
+    d_row, d_col, score, shift = photo_refine(img1, img2, d_map[ir], d_map[ic], refine[0], refine[1], offset=offset,
+                                              min_gain=refine[2], mask=mask, out=(d_map[ir], d_map[ic]),
+                                              return_score=True, return_shift=True)
+    return d_map, score, shift

@@ -39,7 +39,9 @@ class ImageCutSolver():
         smooth_guide='image',
         median=None,
         median_weight=None,
-        photo=None
+        photo=None,
+        refine=None,
+        refine_where='filled'
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -109,6 +111,19 @@ class ImageCutSolver():
             engine.photo_planes(degree_map_mode)
         self.photo_map = None
         self.photo_reject_map = None
+        # (radius, search) or (radius, search, min_gain) of the local re-matching (engine.photo_refine), run
+        # after the fill and before the smoothing: a cell scores the (2 search + 1)^2 integer neighbours of
+        # the position it claims and moves to the best one.  refine_where: 'filled' (only the cells the fill
+        # produced; needs fill=) or 'all'.  Needs 'elevation' and 'elevation2' and no 'distance' in
+        # degree_map_mode.  refine_score_map is the score of the position kept (NaN: not refined),
+        # refine_shift_map the int8 shift [2][H][W] (dy, dx).  None: nothing is refined
+        self.refine = engine.refine_params(refine) if refine is not None else None
+        self.refine_where = refine_where
+        if self.refine is not None:
+            engine.refine_planes(degree_map_mode)
+            engine.refine_where(refine_where, self.fill)
+        self.refine_score_map = None
+        self.refine_shift_map = None
 
         self.log_flg = True
 
@@ -188,7 +203,11 @@ class ImageCutSolver():
         in every mode, after the median and before the speckle filter, and the uint8 mask [H][W] of
         those cells comes immediately before the score.  The chain is stitch -> median -> photo
         reject -> speckle -> fill -> smooth -> photo score, the tuple (d_map, out_map[, err]
-        [, spread, count][, speckles][, holes][[, rejected], score])."""
+        [, spread, count][, speckles][, holes][[, rejected], score]).  With self.refine set the cells
+        are matched again locally (engine.photo_refine) after the fill and before the smoothing --
+        only the filled ones with refine_where='filled' -- and the float64 score and the int8 shift
+        [2][H][W] come immediately before the photo tensors: (d_map, out_map[, err][, spread, count]
+        [, speckles][, holes][, refine score, refine shift][[, rejected], score])."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -210,7 +229,8 @@ class ImageCutSolver():
                                              merge=self.merge, merge_min_count=self.merge_min_count,
                                              speckle=self.speckle, smooth=self.smooth,
                                              smooth_guide=self.smooth_guide, median=self.median,
-                                             median_weight=self.median_weight, photo=self.photo)
+                                             median_weight=self.median_weight, photo=self.photo,
+                                             refine=self.refine, refine_where=self.refine_where)
         if self.merge is not None:
             if self.consistency is not None:
                 fwd, bwd = engine.solve_tiles_bidir(*args)
@@ -240,6 +260,11 @@ class ImageCutSolver():
         if self.fill is not None:
             d, holes = engine.fill_holes(maps[0], self.fill, out=maps[0], return_holes=True)
             maps = (d,) + tuple(maps[1:]) + (holes,)
+        if self.refine is not None:
+            d, rscore, rshift = engine.refine_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.refine,
+                                                    self.exclusive_pix,
+                                                    maps[-1] if self.refine_where == 'filled' else None)
+            maps = (d,) + tuple(maps[1:]) + (rscore, rshift)
         if self.smooth is not None:
             guide = engine.smooth_guide(self.img1, self.exclusive_pix, maps[0]) if self.smooth_guide == 'image' else None
             d = engine.bilateral_filter(maps[0], *self.smooth, guide=guide, out=maps[0])
@@ -261,6 +286,10 @@ class ImageCutSolver():
             if self.photo[1] is not None:  # the cells rejected for scoring below min_score (before any fill)
                 self.photo_reject_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
                 maps = maps[:-1]
+        if self.refine is not None:        # immediately before the photo tensors: taken off next
+            self.refine_shift_map = maps[-1].cpu().numpy() if maps[-1] is not None else None
+            self.refine_score_map = maps[-2].cpu().numpy() if maps[-2] is not None else None
+            maps = maps[:-2]
         d_map, out_map = maps[0], maps[1]
         # (None on the ranks other than 0 of a sharded solve with tile_sharding(result='root'))
         self.d_map = d_map.cpu().numpy() if d_map is not None else None

@@ -385,7 +385,8 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
                         merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
                         smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
-                        medianer=None, photo=None, photoer=None):
+                        medianer=None, photo=None, photoer=None, refine=None, refine_where='filled',
+                        refiner=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -434,13 +435,26 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     min_score, d_map) -> (score, d_map, uint8 mask)``), and the uint8 mask [H][W] comes immediately
     before the score: (d_map, out_map[, err][, spread, count][, speckles][, holes][[, rejected],
     score]).  None: nothing changes.  The chain is stitch -> median -> photo reject -> speckle ->
-    fill -> smooth -> photo score."""
+    fill -> smooth -> photo score.
+    ``refine``: (radius, search) or (radius, search, min_gain), with both 'elevation' and 'elevation2'
+    and no 'distance' in ``modes`` (else ValueError); rank 0 then matches the cells again locally after
+    the fill and before the smoothing (engine.photo_refine with the offset e, or ``refiner(img1, img2,
+    d_row, d_col, radius, search, e, min_gain, mask or None) -> (d_row, d_col, score, int8 shift
+    [2][H][W])``).  ``refine_where``: 'filled' -- only the cells the fill produced in either plane;
+    needs ``fill`` -- or 'all'.  The float64 score [H][W] and the shift come immediately before the
+    photo tensors: (d_map, out_map[, err][, spread, count][, speckles][, holes][, refine score, refine
+    shift][[, rejected], score]).  None: nothing changes.  The chain is stitch -> median -> photo
+    reject -> speckle -> fill -> refine -> smooth -> photo score."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     pho = engine.photo_params(photo) if photo is not None else None
     if pho is not None:
         pho_row, pho_col = engine.photo_planes(modes)
     pho_img1, pho_img2 = img1, img2      # (consistency stacks the pair below)
+    ref = engine.refine_params(refine) if refine is not None else None
+    if ref is not None:
+        ref_row, ref_col = engine.refine_planes(modes)
+        engine.refine_where(refine_where, fill)
     med = engine.median_params(median) if median is not None else None
     if median_weight not in (None, 'correlation'):
         raise ValueError("median_weight must be None or 'correlation'")
@@ -510,6 +524,20 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             else:
                 d, holes = engine.fill_holes(maps[0], iters, out=maps[0], return_holes=True)
             maps = (d,) + tuple(maps[1:]) + (holes,)
+    if ref is not None:
+        nmaps += 2
+        if maps is not None:
+            if refiner is not None:
+                holes = maps[-1] if refine_where == 'filled' else None
+                mask = None if holes is None else (np.asarray(holes[ref_row]) | np.asarray(holes[ref_col]))
+                d_row, d_col, rscore, rshift = refiner(pho_img1, pho_img2, maps[0][ref_row], maps[0][ref_col], ref[0],
+                                                       ref[1], pho_e, ref[2], mask)
+                d = maps[0]
+                d[ref_row], d[ref_col] = d_row, d_col
+            else:
+                d, rscore, rshift = engine.refine_stage(pho_img1, pho_img2, maps[0], modes, ref, pho_e,
+                                                        maps[-1] if refine_where == 'filled' else None)
+            maps = (d,) + tuple(maps[1:]) + (rscore, rshift)
     if smo is not None and maps is not None:
         e = (window_size - 1) // 2
         if smoother is not None:
@@ -545,6 +573,9 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
         if iters is not None:
             out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
+        if ref is not None:
+            out.append(torch.empty((H, W), dtype=torch.float64, device=dev))
+            out.append(torch.empty((2, H, W), dtype=torch.int8, device=dev))
         if pho is not None:
             if pho[1] is not None:
                 out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))

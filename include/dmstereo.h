@@ -562,6 +562,60 @@ int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2
                    double *d_warped /* may be NULL */, uint8_t *d_rejected /* may be NULL */,
                    void *d_work, void *stream);
 
+/* ---- Local re-matching of a disparity map (dm_photo_refine.hip) -----------------------------
+ * Not in the reference.  Rejection turns a wrong cell into a hole and the fill puts a guess
+ * there; dm_photo_refine measures a cell again: it scores the (2s+1)^2 integer neighbours of
+ * the position the map claims with dm_photo_score's correlation and moves the cell to the best
+ * one.  Images, planes, offsets and the radius r in [1, 7] are dm_photo_score's; `search` is s in
+ * [1, 3], min_gain in [0, 2].  Per cell (y, x), (cy, cx) = (y + oy, x + ox):
+ *   1. The cell is skipped if d_mask is given and 0 at the cell, if d_row or d_col is not finite
+ *      (the range test on the double), if the img1 window, rows cy-r .. cy+r and columns
+ *      cx-r .. cx+r, leaves the image, or if py = (double)cy - d_row or px = (double)cx - d_col
+ *      lies outside [-2^30, 2^30] (tested on the double, before any conversion).  A skipped cell
+ *      copies both planes bit for bit, NaN payloads and -0.0 included; its score is NaN
+ *      (0x7ff8000000000000), its shift (0, 0).
+ *   2. iy = floor(py), ix = floor(px), fy = py - iy, fx = px - ix and w0 .. w3 as in
+ *      dm_photo_score's rules 2 and 5.  A candidate is (dy, dx), integers in [-s, s]^2; it is
+ *      scored iff r <= iy+dy <= Hi-r-2 and r <= ix+dx <= Wi-r-2.  Its score is dm_photo_score's
+ *      rules 4 and 5 with the four img2 windows whose top-left corners are (iy+dy-r, ix+dx-r) +
+ *      (0,0), (0,1), (1,0), (1,1) and the same weights: exact integer sums, the float64 tail in
+ *      the same order, clamped to [-1, 1].  So candidate (0, 0) is scored exactly where
+ *      dm_photo_score gives a score that is not NaN, and has that score's bits.
+ *   3. The winner is the scored candidate with the highest score; ties go to the smallest
+ *      dy^2 + dx^2, then the smaller dy, then the smaller dx.  If the centre (0, 0) is scored and
+ *      `winner > centre + min_gain` (one float64 add, one compare) is false, the centre wins.  If
+ *      no candidate is scored the cell is skipped as in 1.
+ *   4. The centre wins: both planes are copied bit for bit, the score is the centre's, the shift
+ *      (0, 0).  A map that is already locally best comes out unchanged to the bit.
+ *   5. Another candidate wins, with score s0: ty = tx = 0.0.  With DM_REFINE_SUBPIX, per axis, if
+ *      both neighbours of the winner along the axis lie in [-s, s] and are scored, with scores sm
+ *      (at -1) and sp (at +1): den = (sm + sp) - 2.0 * s0, and if den < 0, t = (0.5 * (sm - sp)) /
+ *      den, clamped to [-0.5, 0.5].  out_row = d_row - ((double)dy + ty), out_col = d_col -
+ *      ((double)dx + tx).  The score is s0, the shift (dy, dx).
+ *   6. A cell reads only its own d_row and d_col, before it writes: d_out_row and d_out_col may
+ *      alias d_row and d_col.
+ * tests/test_refine_host.py restates this in plain loops; the kernel equals it bit for bit. */
+enum { DM_REFINE_SUBPIX = 1 };
+
+/* Bytes of the workspace dm_photo_refine asks for (a constant 16: the kernel keeps everything on
+ * chip); 0 for a shape it does not take: dm_photo_bytes' limits on H, W, Hi or Wi above 2^30, a
+ * radius outside [1, 7] or a search outside [1, 3]. */
+size_t dm_photo_refine_bytes(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t search);
+
+/* d_mask (uint8 [H][W]), d_score (float64 [H][W]) and d_shift (int8 [2][H][W]: dy, then dx) may
+ * be NULL.  d_work: dm_photo_refine_bytes(...) bytes, not NULL.  DM_ERR_ARG for a null image /
+ * plane / output / workspace, a side below 1, a stride below Wi, an offset outside [-2^30, 2^30],
+ * a radius outside [1, 7], a search outside [1, 3], a min_gain outside [0, 2] (NaN included),
+ * unknown flag bits; DM_ERR_UNSUPPORTED for the other shapes dm_photo_refine_bytes refuses.
+ * Validation precedes every HIP call; nothing is allocated, nothing synchronises, one launch on
+ * `stream`; the result is the same from run to run. */
+int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2, int64_t stride2,
+                    int32_t Hi, int32_t Wi, const double *d_row, const double *d_col, int32_t H, int32_t W,
+                    int32_t oy, int32_t ox, int32_t radius, int32_t search, double min_gain, int32_t flags,
+                    const uint8_t *d_mask /* may be NULL */, double *d_out_row, double *d_out_col,
+                    double *d_score /* may be NULL */, int8_t *d_shift /* may be NULL */,
+                    void *d_work, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -645,7 +699,8 @@ const char *dm_last_error(void);
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
  * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16,
- * dm_level_num_f16, dm_photo_bytes and dm_photo_score are additive entries within 1.10:
+ * dm_level_num_f16, dm_photo_bytes, dm_photo_score, dm_photo_refine_bytes and dm_photo_refine
+ * are additive entries within 1.10:
  * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);
 

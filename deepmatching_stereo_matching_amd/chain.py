@@ -1,0 +1,180 @@
+"""The post-processing chain of a stitched d_map, for ImageCutSolver and shard.solve_image_sharded.
+
+The chain is stitch -> median -> photo reject -> speckle -> fill -> refine -> smooth -> photo
+score (STAGES below is that order in code).  The caller stitches; every stage after that is
+optional, works on d_map [len(modes)][H][W] in place and is switched on by its keyword:
+
+  median        engine.median_filter, all modes in one call, weighted by out_map when
+                median_weight is 'correlation'; holes stay holes.
+  photo reject  with photo=(radius, min_score): the cells whose photo-consistency score
+                (engine.photo_score, map cell (y, x) at image pixel (y + e, x + e)) is below
+                min_score become NaN in every mode; adds the uint8 mask `rejected`.
+  speckle       engine.filter_speckles; adds the uint8 mask `speckles` of the cells removed.
+  fill          engine.fill_holes; adds the uint8 mask `holes` of the cells that were filled.
+  refine        engine.photo_refine on the two elevation planes, of the filled cells only with
+                refine_where='filled'; adds `refine_score` and the int8 `refine_shift`.
+  smooth        engine.bilateral_filter, guided by img1 under the map's cells (smooth_guide
+                'image') or by the map itself ('self'); holes stay holes.
+  photo score   with photo=: adds `score`, the photo-consistency of the final d_map.
+
+The result is a tuple in the order of Chain.layout -- not the order the stages run in:
+(d_map, out_map[, err][, spread, count][, speckles][, holes][, refine_score, refine_shift]
+[[, rejected], score]).  A stage may be replaced by a host function (the hooks of
+solve_image_sharded); the calls are the ones written in the stage functions below.
+"""
+
+from types import SimpleNamespace
+
+import numpy as np
+import torch
+
+from deepmatching_stereo_matching_amd import engine
+
+
+def _median(c, v, r):
+    if c.median is None:
+        return
+    weight = engine.median_weight(c.median_weight, (v['d_map'], v['out_map']))
+    if r.medianer is not None:
+        v['d_map'] = r.medianer(v['d_map'], weight, *c.median)
+    else:
+        v['d_map'] = engine.median_filter(v['d_map'], c.median[0], weight=weight, iters=c.median[1], out=v['d_map'])
+
+
+def _photo_reject(c, v, r):
+    if c.photo is None or c.photo[1] is None:
+        return
+    d = v['d_map']
+    if r.photoer is not None:
+        row, col = engine.photo_planes(c.modes)
+        _, v['d_map'], v['rejected'] = r.photoer(r.img1, r.img2, d[row], d[col], c.photo[0], r.e, c.photo[1], d)
+    else:
+        v['d_map'], v['rejected'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, True)
+
+
+def _speckle(c, v, r):
+    if c.speckle is None:
+        return
+    if r.speckler is not None:
+        v['d_map'], v['speckles'] = r.speckler(v['d_map'], *c.speckle)
+    else:
+        v['d_map'], v['speckles'] = engine.filter_speckles(v['d_map'], *c.speckle, out=v['d_map'],
+                                                           return_removed=True)
+
+
+def _fill(c, v, r):
+    if c.fill is None:
+        return
+    if r.filler is not None:
+        v['d_map'], v['holes'] = r.filler(v['d_map'], c.fill)
+    else:
+        v['d_map'], v['holes'] = engine.fill_holes(v['d_map'], c.fill, out=v['d_map'], return_holes=True)
+
+
+def _refine(c, v, r):
+    if c.refine is None:
+        return
+    d = v['d_map']
+    holes = v['holes'] if c.refine_where == 'filled' else None
+    if r.refiner is not None:
+        row, col = engine.refine_planes(c.modes)
+        mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
+        d[row], d[col], v['refine_score'], v['refine_shift'] = r.refiner(
+            r.img1, r.img2, d[row], d[col], c.refine[0], c.refine[1], r.e, c.refine[2], mask)
+    else:
+        v['d_map'], v['refine_score'], v['refine_shift'] = engine.refine_stage(r.img1, r.img2, d, c.modes, c.refine,
+                                                                              r.e, holes)
+
+
+def _smooth(c, v, r):
+    if c.smooth is None:
+        return
+    d = v['d_map']
+    if r.smoother is not None:
+        H, W = np.shape(d)[-2:]
+        guide = np.asarray(r.img1)[r.e:r.e + H, r.e:r.e + W] if c.smooth_guide == 'image' else None
+        v['d_map'] = r.smoother(d, guide, *c.smooth)
+    else:
+        guide = engine.smooth_guide(r.img1, r.e, d) if c.smooth_guide == 'image' else None
+        v['d_map'] = engine.bilateral_filter(d, *c.smooth, guide=guide, out=d)
+
+
+def _photo_score(c, v, r):
+    if c.photo is None:
+        return
+    d = v['d_map']
+    if r.photoer is not None:
+        row, col = engine.photo_planes(c.modes)
+        v['score'] = r.photoer(r.img1, r.img2, d[row], d[col], c.photo[0], r.e, None, None)
+    else:
+        v['score'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, False)
+
+
+STAGES = (_median, _photo_reject, _speckle, _fill, _refine, _smooth, _photo_score)
+
+
+class Chain:
+    """The validated keywords of the chain (ValueError for a bad one) as attributes of their names,
+    parsed by engine.*_params: None switches a stage off."""
+
+    def __init__(self, modes, fill=None, speckle=None, smooth=None, smooth_guide='image', median=None,
+                 median_weight=None, photo=None, refine=None, refine_where='filled'):
+        self.modes = modes
+        self.fill = engine.fill_iterations(fill) if fill is not None else None
+        self.speckle = engine.speckle_params(speckle) if speckle is not None else None
+        self.smooth = engine.smooth_params(smooth) if smooth is not None else None
+        if smooth_guide not in ('image', 'self'):
+            raise ValueError("smooth_guide must be 'image' or 'self'")
+        self.smooth_guide = smooth_guide
+        self.median = engine.median_params(median) if median is not None else None
+        if median_weight not in (None, 'correlation'):
+            raise ValueError("median_weight must be None or 'correlation'")
+        self.median_weight = median_weight
+        self.photo = engine.photo_params(photo) if photo is not None else None
+        if self.photo is not None:
+            engine.photo_planes(modes)
+        self.refine = engine.refine_params(refine) if refine is not None else None
+        self.refine_where = refine_where
+        if self.refine is not None:
+            engine.refine_planes(modes)
+            engine.refine_where(refine_where, self.fill)
+
+    def layout(self, H, W, consistency, merge):
+        """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
+        cells stitched with the ``consistency`` and ``merge`` keywords of the caller."""
+        M = len(self.modes)
+        f64, u8 = torch.float64, torch.uint8
+        lay = [('d_map', (M, H, W), f64), ('out_map', (H, W), f64)]
+        if consistency is not None:
+            lay.append(('err', (H, W), f64))
+        if merge is not None:
+            lay += [('spread', (M, H, W), f64), ('count', (H, W), u8)]
+        if self.speckle is not None:
+            lay.append(('speckles', (M, H, W), u8))
+        if self.fill is not None:
+            lay.append(('holes', (M, H, W), u8))
+        if self.refine is not None:
+            lay += [('refine_score', (H, W), f64), ('refine_shift', (2, H, W), torch.int8)]
+        if self.photo is not None:
+            if self.photo[1] is not None:
+                lay.append(('rejected', (H, W), u8))
+            lay.append(('score', (H, W), f64))
+        return lay
+
+    def names(self, consistency, merge):
+        """The names of layout()."""
+        return [name for name, _, _ in self.layout(0, 0, consistency, merge)]
+
+    def run(self, stitched, img1, img2, e, consistency, merge, medianer=None, photoer=None, speckler=None,
+            filler=None, refiner=None, smoother=None):
+        """The stages over ``stitched``, the tensors of the stitch: the head of the layout, a merge
+        of one direction without its err -> the result tuple.  ``img1``, ``img2``: the pair as the
+        caller got it (never the stacked one of a two-direction solve); ``e``: the offset of a map
+        cell in the image; a hook replaces the device stage of its name (None: the device stage)."""
+        names = self.names(consistency, merge)
+        v = dict(zip(names, stitched))
+        r = SimpleNamespace(img1=img1, img2=img2, e=int(e), medianer=medianer, photoer=photoer, speckler=speckler,
+                            filler=filler, refiner=refiner, smoother=smoother)
+        for stage in STAGES:
+            stage(self, v, r)
+        return tuple(v[name] for name in names)

@@ -34,32 +34,10 @@
 // (d_out == d_in, odd iters) the input is copied to d_work first.
 #include <hip/hip_runtime.h>
 
-#include <float.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdlib.h>
 
-#include "../../include/dmstereo.h"
 #include "dm_exp.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int bfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define BHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return bfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY, dm_is_hole, dm_nan, dm_maps_plan, dm_tile_env
 
 #define BIL_THREADS 256
 #define BIL_TMAX 32                      // largest tile side
@@ -72,11 +50,6 @@ enum { GK_SELF = 0, GK_F64 = 1, GK_U8 = 2 };
 // (the only pass); 1 where the input is a hole (first of several passes); the entry and the
 // output is finite (last of several passes)
 enum { FM_NONE = 0, FM_ONLY = 1, FM_FIRST = 2, FM_LAST = 3 };
-
-// the range test on the double itself: NaN and +-inf fail it (dm_fill.hip: fill_is_hole)
-__device__ __forceinline__ bool bil_is_hole(double x) { return !(x >= -DBL_MAX && x <= DBL_MAX); }
-
-__device__ __forceinline__ double bil_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // bytes of LDS of one workgroup: value plane, spatial table, then the guide plane / colour table
 static size_t bil_lds(int gk, int T, int r)
@@ -118,16 +91,16 @@ __global__ __launch_bounds__(BIL_THREADS) void k_bilat(const double *in, const v
         const int y = y0 - r + ly, x = x0 - r + lx;
         const bool inside = y >= 0 && y < H && x >= 0 && x < W;
         const size_t c = inside ? (size_t)y * W + x : 0;
-        const double v = inside ? in[c] : bil_nan();
+        const double v = inside ? in[c] : dm_nan();
         if (GK == GK_U8) {
-            const bool usable = !bil_is_hole(v);                // (outside the map: NaN)
+            const bool usable = !dm_is_hole(v);                // (outside the map: NaN)
             Xs[l] = usable ? v : 0.0;
             Gu[l] = usable ? (uint16_t)gu[c] : (uint16_t)BIL_G_OUT;
         } else {
             Xs[l] = v;
             if (GK == GK_F64) {
-                const double g = inside ? gd[c] : bil_nan();
-                Gs[l] = (bil_is_hole(v) || bil_is_hole(g)) ? bil_nan() : g;
+                const double g = inside ? gd[c] : dm_nan();
+                Gs[l] = (dm_is_hole(v) || dm_is_hole(g)) ? dm_nan() : g;
             }
         }
     }
@@ -148,7 +121,7 @@ __global__ __launch_bounds__(BIL_THREADS) void k_bilat(const double *in, const v
         if (y >= H || x >= W) continue;
         const size_t c = (size_t)y * W + x;
         const double xc = in[c];
-        const bool hole = bil_is_hole(xc);
+        const bool hole = dm_is_hole(xc);
         double res = xc;
         bool copy = hole && !fill;
         const int ctr = (ty + r) * LW + tx + r;
@@ -170,7 +143,7 @@ __global__ __launch_bounds__(BIL_THREADS) void k_bilat(const double *in, const v
             }
         } else {
             const double g0 = GK == GK_F64 ? gd[c] : xc;
-            copy = copy || bil_is_hole(g0);
+            copy = copy || dm_is_hole(g0);
             if (!copy) {
                 double num = 0.0, den = 0.0;
                 int k = 0;
@@ -190,9 +163,9 @@ __global__ __launch_bounds__(BIL_THREADS) void k_bilat(const double *in, const v
             }
         }
         out[mbase + c] = res;      // (a copied cell: the double moves unchanged, payload and sign)
-        if (fmode == FM_ONLY) filled[mbase + c] = hole && !bil_is_hole(res) ? 1 : 0;
+        if (fmode == FM_ONLY) filled[mbase + c] = hole && !dm_is_hole(res) ? 1 : 0;
         else if (fmode == FM_FIRST) filled[mbase + c] = hole ? 1 : 0;
-        else if (fmode == FM_LAST) filled[mbase + c] = filled[mbase + c] && !bil_is_hole(res) ? 1 : 0;
+        else if (fmode == FM_LAST) filled[mbase + c] = filled[mbase + c] && !dm_is_hole(res) ? 1 : 0;
     }
 }
 
@@ -200,8 +173,7 @@ __global__ __launch_bounds__(BIL_THREADS) void k_bilat(const double *in, const v
 // false for a shape the entry does not take (the limits of dm_fill_bytes)
 static bool bil_plan(int32_t M, int32_t H, int32_t W, size_t *bytes)
 {
-    if (M < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return false;
-    if (M > 65535 || H > 64 * 65535 || W > 64 * 65535) return false;
+    if (!dm_maps_plan(M, H, W, 64 * 65535)) return false;
     *bytes = ((size_t)M * H * W * sizeof(double) + 15) & ~(size_t)15;      // one plane for the ping-pong
     return true;
 }
@@ -213,12 +185,7 @@ static bool bil_plan(int32_t M, int32_t H, int32_t W, size_t *bytes)
 // 32 forces one, for measurements and tests.
 static int bil_tile_shift(int gk, int32_t M, int32_t H, int32_t W, int r)
 {
-    const char *e = getenv("DM_BILATERAL_TILE");
-    if (e && *e) {
-        const int v = atoi(e);
-        if (v == 16) return 4;
-        if (v == 32) return 5;
-    }
+    if (const int ts = dm_tile_env("DM_BILATERAL_TILE")) return ts;
     const long long tiles = (long long)((H + 31) >> 5) * ((W + 31) >> 5) * M;
     return 8 * bil_lds(gk, 32, r) <= 160 * 1024 && tiles >= 4096 ? 5 : 4;
 }
@@ -248,31 +215,31 @@ int dm_bilateral_filter(const double *d_in, const void *d_guide, int32_t guide_m
                         int32_t W, int32_t radius, double den_color, double den_space, int32_t iters,
                         int32_t flags, double *d_out, uint8_t *d_filled, void *d_work, void *stream)
 {
-    if (!d_in || !d_out || !d_work) return bfail(DM_ERR_ARG, "null input / output / workspace pointer");
-    if (M < 1 || H < 1 || W < 1) return bfail(DM_ERR_ARG, "bad bilateral shape M=%d H=%d W=%d", M, H, W);
-    if (radius < 1 || radius > BIL_RMAX) return bfail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", BIL_RMAX, radius);
-    if (iters < 1 || iters > 64) return bfail(DM_ERR_ARG, "iters must be in [1, 64] (got %d)", iters);
-    if (!(den_color > 0.0)) return bfail(DM_ERR_ARG, "den_color must be > 0 (got %g)", den_color);
-    if (!(den_space > 0.0)) return bfail(DM_ERR_ARG, "den_space must be > 0 (got %g)", den_space);
-    if (flags & ~(DM_BILAT_FILL | DM_BILAT_GUIDE_U8)) return bfail(DM_ERR_ARG, "unknown flags 0x%x", flags);
+    if (!d_in || !d_out || !d_work) return dm_fail(DM_ERR_ARG, "null input / output / workspace pointer");
+    if (M < 1 || H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad bilateral shape M=%d H=%d W=%d", M, H, W);
+    if (radius < 1 || radius > BIL_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", BIL_RMAX, radius);
+    if (iters < 1 || iters > 64) return dm_fail(DM_ERR_ARG, "iters must be in [1, 64] (got %d)", iters);
+    if (!(den_color > 0.0)) return dm_fail(DM_ERR_ARG, "den_color must be > 0 (got %g)", den_color);
+    if (!(den_space > 0.0)) return dm_fail(DM_ERR_ARG, "den_space must be > 0 (got %g)", den_space);
+    if (flags & ~(DM_BILAT_FILL | DM_BILAT_GUIDE_U8)) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     if (d_guide) {
         if (guide_maps != 1 && guide_maps != M)
-            return bfail(DM_ERR_ARG, "guide_maps must be 1 or M=%d (got %d)", M, guide_maps);
+            return dm_fail(DM_ERR_ARG, "guide_maps must be 1 or M=%d (got %d)", M, guide_maps);
     } else if (flags & (DM_BILAT_FILL | DM_BILAT_GUIDE_U8)) {
-        return bfail(DM_ERR_ARG, "flags 0x%x need a guide", flags);
+        return dm_fail(DM_ERR_ARG, "flags 0x%x need a guide", flags);
     }
     size_t bytes;
     if (!bil_plan(M, H, W, &bytes))
-        return bfail(DM_ERR_UNSUPPORTED,
+        return dm_fail(DM_ERR_UNSUPPORTED,
                      "bilateral filter of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)", M, H, W);
     hipStream_t st = (hipStream_t)stream;
     static bool attr_set = false; // idempotent attributes, benign race
     if (!attr_set) {
-        BHIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_SELF>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_SELF>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)bil_lds(GK_SELF, BIL_TMAX, BIL_RMAX)));
-        BHIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_F64>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)bil_lds(GK_F64, BIL_TMAX, BIL_RMAX)));
-        BHIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_U8>, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_bilat<GK_U8>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)bil_lds(GK_U8, BIL_TMAX, BIL_RMAX)));
         attr_set = true;
     }
@@ -283,7 +250,7 @@ int dm_bilateral_filter(const double *d_in, const void *d_guide, int32_t guide_m
     // pass p writes d_out when an even number of passes follow it, else d_work
     const double *src = d_in;
     if (d_in == d_out && (iters & 1)) {      // the first pass would read what it writes
-        BHIP_TRY(hipMemcpyAsync(work, d_in, (size_t)M * H * W * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DM_HIP_TRY(hipMemcpyAsync(work, d_in, (size_t)M * H * W * sizeof(double), hipMemcpyDeviceToDevice, st));
         src = work;
     }
     for (int p = 0; p < iters; ++p) {
@@ -296,7 +263,7 @@ int dm_bilateral_filter(const double *d_in, const void *d_guide, int32_t guide_m
             e = bil_launch<GK_F64>(src, d_guide, guide_maps, M, H, W, ts, radius, den_color, den_space, fill, fmode, dst, d_filled, st);
         else
             e = bil_launch<GK_SELF>(src, nullptr, 1, M, H, W, ts, radius, den_color, den_space, fill, fmode, dst, d_filled, st);
-        BHIP_TRY(e);
+        DM_HIP_TRY(e);
         src = dst;
     }
     return DM_OK;

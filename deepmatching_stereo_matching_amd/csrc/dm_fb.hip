@@ -21,29 +21,9 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
 
-#include "../../include/dmstereo.h"
 #include "dm_fb_err.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int ffail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define FHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return ffail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY
 
 // masked may be NULL or alias fwd: a thread reads its own forward cell before it writes it,
 // and no other thread reads that cell
@@ -112,7 +92,7 @@ __global__ void k_stitch_fb(const double *fwd, const double *bwd, int n0, int n1
 
 static int check_tol(double tol)
 {
-    if (!(tol >= 0.0)) return ffail(DM_ERR_ARG, "tolerance must be >= 0 (got %g)", tol);
+    if (!(tol >= 0.0)) return dm_fail(DM_ERR_ARG, "tolerance must be >= 0 (got %g)", tol);
     return DM_OK;
 }
 
@@ -120,7 +100,7 @@ static int check_tol(double tol)
 static int fb_blocks(unsigned long long n, unsigned *blocks)
 {
     const unsigned long long nb = (n + 255) / 256;
-    if (nb > 0x7fffffffull) return ffail(DM_ERR_UNSUPPORTED, "map of %llu cells", n);
+    if (nb > 0x7fffffffull) return dm_fail(DM_ERR_UNSUPPORTED, "map of %llu cells", n);
     *blocks = (unsigned)nb;
     return DM_OK;
 }
@@ -130,15 +110,15 @@ extern "C" {
 int dm_fb_check(const double *d_fwd, const double *d_bwd, int32_t T, int32_t h, int32_t w, double tol,
                 double *d_err, double *d_masked, void *stream)
 {
-    if (!d_fwd || !d_bwd || !d_err) return ffail(DM_ERR_ARG, "null forward / backward / error pointer");
-    if (T < 1 || h < 1 || w < 1) return ffail(DM_ERR_ARG, "bad fb_check shape T=%d h=%d w=%d", T, h, w);
+    if (!d_fwd || !d_bwd || !d_err) return dm_fail(DM_ERR_ARG, "null forward / backward / error pointer");
+    if (T < 1 || h < 1 || w < 1) return dm_fail(DM_ERR_ARG, "bad fb_check shape T=%d h=%d w=%d", T, h, w);
     int rc = check_tol(tol);
     if (rc) return rc;
     unsigned nb;
     rc = fb_blocks((unsigned long long)T * (unsigned long long)h * (unsigned long long)w, &nb);
     if (rc) return rc;
     k_fb_check<<<nb, 256, 0, (hipStream_t)stream>>>(d_fwd, d_bwd, T, h, w, tol, d_err, d_masked);
-    FHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -148,22 +128,22 @@ int dm_stitch_fb(const double *d_fwd, const double *d_bwd, int32_t n0, int32_t n
 {
     if (!d_fwd || !d_bwd || !d_dmap || !d_score || !d_err || n0 < 1 || n1 < 1 || h0 < 1 || w0 < 1 ||
         stride0 < 1 || stride1 < 1 || nmodes < 0 || nmodes > 8 || (nmodes && !modes))
-        return ffail(DM_ERR_ARG, "bad stitch arguments");
+        return dm_fail(DM_ERR_ARG, "bad stitch arguments");
     FbModes m;
     for (int k = 0; k < 8; ++k) m.m[k] = k < nmodes ? modes[k] : 0;
     for (int k = 0; k < nmodes; ++k)
-        if (m.m[k] < 0 || m.m[k] > 2) return ffail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
+        if (m.m[k] < 0 || m.m[k] > 2) return dm_fail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
     int rc = check_tol(tol);
     if (rc) return rc;
     const long long Hout = (long long)stride0 * (n0 - 1) + h0, Wout = (long long)stride1 * (n1 - 1) + w0;
     if (Hout > 0x7fffffffLL || Wout > 0x7fffffffLL)
-        return ffail(DM_ERR_UNSUPPORTED, "stitched map of %lld x %lld cells", Hout, Wout);
+        return dm_fail(DM_ERR_UNSUPPORTED, "stitched map of %lld x %lld cells", Hout, Wout);
     unsigned nb;
     rc = fb_blocks((unsigned long long)Hout * (unsigned long long)Wout, &nb);
     if (rc) return rc;
     k_stitch_fb<<<nb, 256, 0, (hipStream_t)stream>>>(d_fwd, d_bwd, n0, n1, h0, w0, stride0, stride1, m, nmodes, tol,
                                                      d_dmap, d_score, d_err, (int)Hout, (int)Wout);
-    FHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

@@ -30,31 +30,9 @@
 // reads the same from either.
 #include <hip/hip_runtime.h>
 
-#include <float.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdlib.h>
 
-#include "../../include/dmstereo.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int lfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define LHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return lfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY, dm_is_hole, dm_maps_plan
 
 #define FILL_T 64                       // tile side of k_fill_tile
 #define FILL_K 16                       // its largest halo = Jacobi steps per launch
@@ -68,9 +46,6 @@ static int lfail(int code, const char *fmt, ...)
 static constexpr size_t FILL_TILE_LDS = (size_t)FILL_R * FILL_R * (2 * sizeof(double) + 1);
 static constexpr size_t FILL_TOP_LDS = (size_t)FILL_TOPCAP * (sizeof(double) + sizeof(uint32_t)) +
                                        (size_t)FILL_TOPC * sizeof(double);
-
-// the range test on the double itself: NaN and +-inf fail it
-__device__ __forceinline__ bool fill_is_hole(double x) { return !(x >= -DBL_MAX && x <= DBL_MAX); }
 
 __device__ __forceinline__ double fill_pull_cell(double v00, double v01, double v10, double v11, uint32_t n00,
                                                  uint32_t n01, uint32_t n10, uint32_t n11, uint32_t *m)
@@ -140,7 +115,7 @@ __global__ __launch_bounds__(256) void k_fill_pull(const double *src, const uint
                         cv[q] = x;
                         cn[q] = srcn[g];
                     } else {
-                        const bool hole = fill_is_hole(x);
+                        const bool hole = dm_is_hole(x);
                         hole0[g] = hole ? 1 : 0;
                         cv[q] = hole ? 0.0 : x;
                         cn[q] = hole ? 0 : 1;
@@ -223,7 +198,7 @@ __global__ __launch_bounds__(FILL_THREADS) void k_fill_top(const double *src, co
             V[l] = x;
             N[l] = srcn[l];
         } else {
-            const bool hole = fill_is_hole(x);
+            const bool hole = dm_is_hole(x);
             V[l] = hole ? 0.0 : x;
             N[l] = hole ? 0 : 1;
             if (holes) holes[l] = hole ? 1 : 0;
@@ -370,8 +345,7 @@ static size_t fill_take(size_t *off, size_t bytes)
 // false for a shape the entry does not take
 static bool fill_plan(int32_t M, int32_t H, int32_t W, FillPlan *p)
 {
-    if (M < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return false;
-    if (M > 65535 || H > 64 * 65535 || W > 64 * 65535) return false;      // grid y / z
+    if (!dm_maps_plan(M, H, W, 64 * 65535)) return false;      // grid y / z
     int k = 0;
     p->h[0] = H;
     p->w[0] = W;
@@ -420,19 +394,19 @@ size_t dm_fill_bytes(int32_t M, int32_t H, int32_t W)
 int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t iters, double *d_out,
                   uint8_t *d_holes, void *d_work, void *stream)
 {
-    if (!d_in || !d_out || !d_work) return lfail(DM_ERR_ARG, "null input / output / workspace pointer");
-    if (M < 1 || H < 1 || W < 1) return lfail(DM_ERR_ARG, "bad fill shape M=%d H=%d W=%d", M, H, W);
-    if (iters < 0 || iters > 4096) return lfail(DM_ERR_ARG, "iterations must be in [0, 4096] (got %d)", iters);
+    if (!d_in || !d_out || !d_work) return dm_fail(DM_ERR_ARG, "null input / output / workspace pointer");
+    if (M < 1 || H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad fill shape M=%d H=%d W=%d", M, H, W);
+    if (iters < 0 || iters > 4096) return dm_fail(DM_ERR_ARG, "iterations must be in [0, 4096] (got %d)", iters);
     FillPlan p;
     if (!fill_plan(M, H, W, &p))
-        return lfail(DM_ERR_UNSUPPORTED, "fill of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)",
+        return dm_fail(DM_ERR_UNSUPPORTED, "fill of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)",
                      M, H, W);
     hipStream_t st = (hipStream_t)stream;
     static bool attr_set = false; // idempotent attributes, benign race
     if (!attr_set) {
-        LHIP_TRY(hipFuncSetAttribute((const void *)k_fill_top, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_fill_top, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)FILL_TOP_LDS));
-        LHIP_TRY(hipFuncSetAttribute((const void *)k_fill_tile, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_fill_tile, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)FILL_TILE_LDS));
         attr_set = true;
     }
@@ -440,7 +414,7 @@ int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t i
     uint32_t *total = (uint32_t *)(ws + p.total);
     if (p.ktop == 0) {      // the whole pyramid in one launch
         k_fill_top<<<M, FILL_THREADS, FILL_TOP_LDS, st>>>(d_in, nullptr, H, W, iters, d_out, d_holes, total);
-        LHIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         return DM_OK;
     }
     uint8_t *hole0 = d_holes ? d_holes : (uint8_t *)(ws + p.hole0);
@@ -458,13 +432,13 @@ int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t i
         const dim3 grid((p.w[s] + 63) / 64, (p.h[s] + 63) / 64, M);
         k_fill_pull<<<grid, 256, 0, st>>>(s ? (const double *)(ws + p.v[s]) : d_in,
                                           s ? (const uint32_t *)(ws + p.n[s]) : nullptr, p.h[s], p.w[s], nl, hole0, o);
-        LHIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         s += nl;
     }
     double *parent = (double *)(ws + p.v[p.ktop]);
     k_fill_top<<<M, FILL_THREADS, FILL_TOP_LDS, st>>>(parent, (const uint32_t *)(ws + p.n[p.ktop]), p.h[p.ktop],
                                                       p.w[p.ktop], iters, parent, nullptr, total);
-    LHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     const int per = fill_steps_per_launch();
     const int launches = iters ? (iters + per - 1) / per : 1;
     for (int k = p.ktop - 1; k >= 0; --k) {
@@ -480,7 +454,7 @@ int dm_fill_holes(const double *d_in, int32_t M, int32_t H, int32_t W, int32_t i
             double *dst = buf[(k ? j : launches - 1 - j) & 1];
             k_fill_tile<<<grid, FILL_THREADS, FILL_TILE_LDS, st>>>(src, j == 0, hole, parent, p.h[k + 1], p.w[k + 1],
                                                                    dst, p.h[k], p.w[k], steps, k ? nullptr : total);
-            LHIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
             done += steps;
             src = dst;
         }

@@ -19,7 +19,7 @@
 
 #include <type_traits>
 
-#include "../../include/dmstereo.h"
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY
 #include "dm_pow.h"
 
 __constant__ double c_pow_tab[DM_POW_NT * 3] = DM_POW_TAB_INIT;
@@ -1255,37 +1255,22 @@ __global__ void k_stitch(const double *match, int n0, int n1, int h0, int w0, in
 // ------------------------------------------------------------------------------------
 static thread_local char g_err[512];
 
-// shared with dm_postproc.hip (not exported)
+// what dm_fail of every .hip file writes through (dm_host.h; not exported)
 __attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap)
 {
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     return code;
 }
 
-static int fail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(x)                                                                          \
-    do {                                                                                    \
-        hipError_t e_ = (x);                                                                \
-        if (e_ != hipSuccess) return fail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
-
 static int check_tiles(const dm_tiles *b)
 {
-    if (!b || !b->d_img1 || !b->d_img2 || !b->d_origins) return fail(DM_ERR_ARG, "null tile batch / pointer");
-    if (b->T < 1 || b->h0 < 1 || b->w0 < 1) return fail(DM_ERR_ARG, "empty batch (T=%d, h0=%d, w0=%d)", b->T, b->h0, b->w0);
+    if (!b || !b->d_img1 || !b->d_img2 || !b->d_origins) return dm_fail(DM_ERR_ARG, "null tile batch / pointer");
+    if (b->T < 1 || b->h0 < 1 || b->w0 < 1) return dm_fail(DM_ERR_ARG, "empty batch (T=%d, h0=%d, w0=%d)", b->T, b->h0, b->w0);
     if (b->ws < 1 || (b->ws & 1) == 0)
-        return fail(DM_ERR_SHAPE, "window_size must be odd (got %d): Correlation_map.py:63-64 broadcast error", b->ws);
-    if (b->ws > 15) return fail(DM_ERR_UNSUPPORTED, "window_size %d > 15 not supported", b->ws);
+        return dm_fail(DM_ERR_SHAPE, "window_size must be odd (got %d): Correlation_map.py:63-64 broadcast error", b->ws);
+    if (b->ws > 15) return dm_fail(DM_ERR_UNSUPPORTED, "window_size %d > 15 not supported", b->ws);
     if (b->method != DM_TM_CCOEFF && b->method != DM_TM_CCOEFF_NORMED)
-        return fail(DM_ERR_ARG, "invalid feature method %d", b->method);
+        return dm_fail(DM_ERR_ARG, "invalid feature method %d", b->method);
     return DM_OK;
 }
 
@@ -1535,13 +1520,13 @@ static int launch_level1(const dm_tiles *b, Stats s, double *L1, hipStream_t st)
     const size_t lds = k2_lds_bytes(b->h0, b->w0, WS);
     static bool attr_set = false; // idempotent attribute, benign race
     if (!attr_set) {
-        HIP_TRY(hipFuncSetAttribute((const void *)k_level1_generic<WS>,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_level1_generic<WS>,
                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     dim3 grid((b->h0 / 2) * (b->w0 / 2), b->T);
     k_level1_generic<WS><<<grid, K2_THREADS, lds, st>>>(make_geo(b), s, L1);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -1589,11 +1574,11 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
     if (KS == 1 && GW == 4 && NW == 4) {
         constexpr int NBc = DM_C5_NB;
         const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
+        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
         if (Bs && (DM_S2 & 4)) k_level12_strip<4, NBc, L2F, CL, 4><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
         else if (Bs) k_level1_mfq<1, 4, 4 * NBc, 4, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
         else k_level1_mfq<1, 4, 4 * NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        HIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         return DM_OK;
     }
     // GW = 4 with one wave per cell block (S = 64, C2): C2_NB cell blocks per workgroup share
@@ -1603,11 +1588,11 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
     if (KS == 1 && GW == 4 && NW == 1) {
         constexpr int NBc = DM_C2_NB;
         const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
+        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
         if (Bs && (DM_S2 & 1)) k_level12_strip<1, NBc, L2F, CL, 4><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
         else if (Bs) k_level1_mfq<1, 4, NBc, 4, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
         else k_level1_mfq<1, 4, NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        HIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         return DM_OK;
     }
     // GW = 4 with 2 waves (C3): 20 KB of LDS (the exchange arrays in the pow tables' hole)
@@ -1615,7 +1600,7 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
     if (KS == 1 && GW == 4 && NW == 2) {
         constexpr int NBc = DM_C3_NB;
         const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
+        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
         if (Bs && (DM_S2 & 2)) k_level12_strip<2, NBc, L2F, CL, DM_C3_MW><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
         // level 1 not stored: the child pows pruned to the level-2 window maxima (dm_prune.h;
         // DM_PRUNE, off: measured slower)
@@ -1625,11 +1610,11 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
         }
         else if (Bs) k_level1_mfq<1, 4, 2 * NBc, DM_C3_MINW, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
         else k_level1_mfq<1, 4, 2 * NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        HIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         return DM_OK;
     }
     // GW = 2 (ws > 5, or widths without a 4-tile split): register budget 5 waves/SIMD
-#define DM_MQ(KS_, GW_, NW_) if (KS == KS_ && GW == GW_ && NW == NW_) { k_level1_mfq<KS_, GW_, NW_, 5, L2F, YF><<<grid, 64 * NW_, 0, st>>>(gg, s, Bw, QS, L1, L2); HIP_TRY(hipGetLastError()); return DM_OK; }
+#define DM_MQ(KS_, GW_, NW_) if (KS == KS_ && GW == GW_ && NW == NW_) { k_level1_mfq<KS_, GW_, NW_, 5, L2F, YF><<<grid, 64 * NW_, 0, st>>>(gg, s, Bw, QS, L1, L2); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
     DM_MQ(1, 2, 1) DM_MQ(1, 2, 2) DM_MQ(1, 2, 4) DM_MQ(1, 2, 8)
     if constexpr (!YF) {
         DM_MQ(2, 2, 1) DM_MQ(2, 2, 2) DM_MQ(2, 2, 4) DM_MQ(2, 2, 8)
@@ -1637,7 +1622,7 @@ static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2
         DM_MQ(4, 2, 1) DM_MQ(4, 2, 2) DM_MQ(4, 2, 4) DM_MQ(4, 2, 8)
     }
 #undef DM_MQ
-    return fail(DM_ERR_UNSUPPORTED, "no column-split instance for KS=%d GW=%d NW=%d", KS, GW, NW);
+    return dm_fail(DM_ERR_UNSUPPORTED, "no column-split instance for KS=%d GW=%d NW=%d", KS, GW, NW);
 }
 
 // the packed-f32 y (YF) needs n <= 25 (see y_of_acc)
@@ -1730,7 +1715,7 @@ static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT
     const int GW = (int)(16 / sizeof(OT)) < G ? (int)(16 / sizeof(OT)) : G;   // = k_volume_ls's GW
     if (b->ws == 5) k_prep_windows16<5><<<nblk(n, 256), 256, 0, st>>>(make_geo(b), G, GW, 1, Bw, QS);
     else k_prep_windows16<0><<<nblk(n, 256), 256, 0, st>>>(make_geo(b), G, GW, 1, Bw, QS);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     const unsigned grid = (unsigned)(b->T * bpt / nw);
     const Geo gg = make_geo(b);
     if (G == 8) {
@@ -1740,14 +1725,14 @@ static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT
                 if (bpt % NWh) return DM_ERR_UNSUPPORTED;
                 k_volume_ls<8, NWh, DM_VL_H_NT, OT, DM_VL_H_TR><<<(unsigned)(b->T * bpt / NWh), 64 * NWh, 0, st>>>(
                     gg, s, Bw, QS, out, have_mm, Bs, Ss);
-                HIP_TRY(hipGetLastError());
+                DM_HIP_TRY(hipGetLastError());
                 return DM_OK;
             }
             if constexpr (DM_VL_HS_NW != 8 || DM_VL_HS_TR != 0) {
                 constexpr int NWs = DM_VL_HS_NW;
                 if (bpt % NWs) return DM_ERR_UNSUPPORTED;
                 k_volume_ls<8, NWs, true, OT, DM_VL_HS_TR><<<(unsigned)(b->T * bpt / NWs), 64 * NWs, 0, st>>>(gg, s, Bw, QS, out, have_mm, Bs, Ss);
-                HIP_TRY(hipGetLastError());
+                DM_HIP_TRY(hipGetLastError());
                 return DM_OK;
             }
         } else {
@@ -1755,7 +1740,7 @@ static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT
             if (bpt % NWf) return DM_ERR_UNSUPPORTED;
             k_volume_ls<8, NWf, DM_VL_F_NT, OT, DM_VL_F_TR, DM_VL_F_MW><<<(unsigned)(b->T * bpt / NWf), 64 * NWf, 0, st>>>(
                 gg, s, Bw, QS, out, have_mm, Bs, Ss);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
             return DM_OK;
         }
     }
@@ -1766,16 +1751,16 @@ static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT
                 if (bpt % NWh) return DM_ERR_UNSUPPORTED;
                 k_volume_ls<16, NWh, true, OT, DM_VL_H2_TR><<<(unsigned)(b->T * bpt / NWh), 64 * NWh, 0, st>>>(
                     gg, s, Bw, QS, out, have_mm, Bs, Ss);
-                HIP_TRY(hipGetLastError());
+                DM_HIP_TRY(hipGetLastError());
                 return DM_OK;
             }
         } else {
             k_volume_ls<16, 8, true, OT, DM_VL_F2_TR, DM_VL_F2_MW><<<grid, 64 * 8, 0, st>>>(gg, s, Bw, QS, out, have_mm, Bs, Ss);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
             return DM_OK;
         }
     }
-#define DM_VL(G_) if (G == G_) { k_volume_ls<G_, 8, true, OT><<<grid, 64 * 8, 0, st>>>(gg, s, Bw, QS, out, have_mm, Bs, Ss); HIP_TRY(hipGetLastError()); return DM_OK; }
+#define DM_VL(G_) if (G == G_) { k_volume_ls<G_, 8, true, OT><<<grid, 64 * 8, 0, st>>>(gg, s, Bw, QS, out, have_mm, Bs, Ss); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
     DM_VL(2) DM_VL(4) DM_VL(8) DM_VL(16)
 #undef DM_VL
     return DM_ERR_UNSUPPORTED;
@@ -1794,7 +1779,7 @@ static int launch_volume_mfq(const dm_tiles *b, void *d_stats, const Stats &s, O
     const unsigned vgrid = (unsigned)((waves + 3) / 4);
     const bool lds = b->w0 <= 128;
     const Geo gg = make_geo(b);
-#define DM_VQ(KS_, LS_) if (KS == KS_ && GW == 2 && lds == LS_) { k_volume_mfq<KS_, 2, false, true, LS_, OT><<<vgrid, 256, 0, st>>>(gg, s, Bw, QS, out); HIP_TRY(hipGetLastError()); return DM_OK; }
+#define DM_VQ(KS_, LS_) if (KS == KS_ && GW == 2 && lds == LS_) { k_volume_mfq<KS_, 2, false, true, LS_, OT><<<vgrid, 256, 0, st>>>(gg, s, Bw, QS, out); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
     DM_VQ(1, true) DM_VQ(1, false) DM_VQ(2, true) DM_VQ(2, false)
     DM_VQ(3, true) DM_VQ(3, false) DM_VQ(4, true) DM_VQ(4, false)
 #undef DM_VQ
@@ -1821,8 +1806,8 @@ const char *dm_build_config(void)
 // stamps of the last launch, {shader start, shader end, real start, real end} per workgroup
 int dm_diag_clock_stamps(unsigned long long *host, int nwg)
 {
-    if (nwg < 0 || nwg > 65536) return fail(DM_ERR_ARG, "nwg %d outside 0 .. 65536", nwg);
-    HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(dm_clock_stamps), (size_t)nwg * 4 * sizeof(unsigned long long)));
+    if (nwg < 0 || nwg > 65536) return dm_fail(DM_ERR_ARG, "nwg %d outside 0 .. 65536", nwg);
+    DM_HIP_TRY(hipMemcpyFromSymbol(host, HIP_SYMBOL(dm_clock_stamps), (size_t)nwg * 4 * sizeof(unsigned long long)));
     return DM_OK;
 }
 #endif
@@ -1852,11 +1837,11 @@ int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats) return fail(DM_ERR_ARG, "null stats workspace");
+    if (!d_stats) return dm_fail(DM_ERR_ARG, "null stats workspace");
     const int P = b->h0 * b->w0;
     dim3 grid(nblk(P, 256), b->T);
     k_stats<<<grid, 256, 0, (hipStream_t)stream>>>(make_geo(b), stats_view(d_stats, b->T, P));
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     const int var = level1_variant(b);
     if (var) { // MFMA-B-ordered windows + packed per-window stats for dm_corr_level1
         dm_v4i *Bw;
@@ -1868,11 +1853,11 @@ int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
         if (f16y_shape(b)) {
             if (b->ws == 5) k_prep_windows16<5, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             else k_prep_windows16<0, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
         } else if (!strip2_shape(b)) {
             if (b->ws == 5) k_prep_windows16<5><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             else k_prep_windows16<0><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
         }
         if (strip_shape(b)) {
             dm_v4i *Bs, *Ss;
@@ -1880,7 +1865,7 @@ int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
             const size_t ns = (size_t)b->T * (b->h0 / 2) * b->w0;
             if (b->ws == 5) k_prep_strips<5><<<nblk(ns, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), Bs, Ss);
             else k_prep_strips<0><<<nblk(ns, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), Bs, Ss);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
         }
     }
     return DM_OK;
@@ -1890,16 +1875,16 @@ int dm_corr_level1(const dm_tiles *b, void *d_stats, double *d_level1, void *str
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats || !d_level1) return fail(DM_ERR_ARG, "null workspace / output");
+    if (!d_stats || !d_level1) return dm_fail(DM_ERR_ARG, "null workspace / output");
     if ((b->h0 & 1) || (b->w0 & 1))
-        return fail(DM_ERR_SHAPE, "could not broadcast: map sides %dx%d must be even (Correlation_map.py:96-103)", b->h0, b->w0);
+        return dm_fail(DM_ERR_SHAPE, "could not broadcast: map sides %dx%d must be even (Correlation_map.py:96-103)", b->h0, b->w0);
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     hipStream_t st = (hipStream_t)stream;
     const int var = level1_variant(b);
     if (var == 3) return launch_mfq<false>(b, d_stats, d_level1, nullptr, st);
     if (P > DM_GENERIC_MAX_P || k2_lds_bytes(b->h0, b->w0, b->ws) > 160 * 1024)
-        return fail(DM_ERR_UNSUPPORTED, "tile too large for the generic level-1 kernel (P=%d)", P);
+        return dm_fail(DM_ERR_UNSUPPORTED, "tile too large for the generic level-1 kernel (P=%d)", P);
     switch (b->ws) {
     case 1: return launch_level1<1>(b, s, d_level1, st);
     case 3: return launch_level1<3>(b, s, d_level1, st);
@@ -1910,16 +1895,16 @@ int dm_corr_level1(const dm_tiles *b, void *d_stats, double *d_level1, void *str
     case 13: return launch_level1<13>(b, s, d_level1, st);
     case 15: return launch_level1<15>(b, s, d_level1, st);
     }
-    return fail(DM_ERR_UNSUPPORTED, "window size %d", b->ws);
+    return dm_fail(DM_ERR_UNSUPPORTED, "window size %d", b->ws);
 }
 
 int dm_corr_level12(const dm_tiles *b, void *d_stats, double *d_level1, double *d_level2, void *stream)
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats || !d_level2) return fail(DM_ERR_ARG, "null workspace / output");
+    if (!d_stats || !d_level2) return dm_fail(DM_ERR_ARG, "null workspace / output");
     if (level1_variant(b) != 3)
-        return fail(DM_ERR_UNSUPPORTED, "fused level-1/level-2 kernel needs h0 %% 4 == 0, w0 %% 32 == 0, w0 <= 256, ws <= 15 (got %dx%d, ws %d)",
+        return dm_fail(DM_ERR_UNSUPPORTED, "fused level-1/level-2 kernel needs h0 %% 4 == 0, w0 %% 32 == 0, w0 <= 256, ws <= 15 (got %dx%d, ws %d)",
                     b->h0, b->w0, b->ws);
     return launch_mfq<true>(b, d_stats, d_level1, d_level2, (hipStream_t)stream);
 }
@@ -1928,7 +1913,7 @@ static int volume_f32(const dm_tiles *b, void *d_stats, float *d_l0, void *strea
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats || !d_l0) return fail(DM_ERR_ARG, "null workspace / output");
+    if (!d_stats || !d_l0) return dm_fail(DM_ERR_ARG, "null workspace / output");
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     dim3 grid(P, b->T);
@@ -1939,9 +1924,9 @@ static int volume_f32(const dm_tiles *b, void *d_stats, float *d_l0, void *strea
         if (rc != DM_ERR_UNSUPPORTED) return rc;
     }
     k_minmax<<<grid, 256, 0, (hipStream_t)stream>>>(make_geo(b), s);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     k_volume<float><<<grid, 256, 0, (hipStream_t)stream>>>(make_geo(b), s, d_l0);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -1949,7 +1934,7 @@ static int volume_f16(const dm_tiles *b, void *d_stats, uint16_t *d_l0, void *st
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats || !d_l0) return fail(DM_ERR_ARG, "null workspace / output");
+    if (!d_stats || !d_l0) return dm_fail(DM_ERR_ARG, "null workspace / output");
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     _Float16 *out = (_Float16 *)d_l0;
@@ -1962,9 +1947,9 @@ static int volume_f16(const dm_tiles *b, void *d_stats, uint16_t *d_l0, void *st
     }
     dim3 grid(P, b->T);
     k_minmax<<<grid, 256, 0, st>>>(make_geo(b), s);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     k_volume<_Float16><<<grid, 256, 0, st>>>(make_geo(b), s, out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -1980,7 +1965,7 @@ int dm_corr_volume_f16(const dm_tiles *b, void *d_stats, uint16_t *d_l0, void *s
 
 int dm_corr_volume_ex(const dm_tiles *b, void *d_stats, int32_t flags, void *d_l0, void *stream)
 {
-    if (flags & ~(DM_VOLUME_F16 | DM_VOLUME_MINMAX_KNOWN)) return fail(DM_ERR_ARG, "unknown volume flags 0x%x", flags);
+    if (flags & ~(DM_VOLUME_F16 | DM_VOLUME_MINMAX_KNOWN)) return dm_fail(DM_ERR_ARG, "unknown volume flags 0x%x", flags);
     const int mm = (flags & DM_VOLUME_MINMAX_KNOWN) != 0;
     if (flags & DM_VOLUME_F16) return volume_f16(b, d_stats, (uint16_t *)d_l0, stream, mm);
     return volume_f32(b, d_stats, (float *)d_l0, stream, mm);
@@ -1988,26 +1973,26 @@ int dm_corr_volume_ex(const dm_tiles *b, void *d_stats, int32_t flags, void *d_l
 
 int dm_rectify_f16(const uint16_t *d_in, size_t n, double *d_out, void *stream)
 {
-    if (!d_in || !d_out) return fail(DM_ERR_ARG, "null pointer");
+    if (!d_in || !d_out) return dm_fail(DM_ERR_ARG, "null pointer");
     if (n == 0) return DM_OK;
     k_rectify<_Float16><<<nblk(n, 256) > 8192 ? 8192 : nblk(n, 256), 256, 0, (hipStream_t)stream>>>(
         (const _Float16 *)d_in, n, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_rectify(const float *d_in, size_t n, double *d_out, void *stream)
 {
-    if (!d_in || !d_out) return fail(DM_ERR_ARG, "null pointer");
+    if (!d_in || !d_out) return dm_fail(DM_ERR_ARG, "null pointer");
     if (n == 0) return DM_OK;
     k_rectify<float><<<nblk(n, 256) > 8192 ? 8192 : nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_in, n, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_out, void *stream)
 {
-    if ((!d_in || !d_out) && n) return fail(DM_ERR_ARG, "null input / output");
+    if ((!d_in || !d_out) && n) return dm_fail(DM_ERR_ARG, "null input / output");
     if (!n) return DM_OK;
     const unsigned grid = nblk(n, 256) > 1024 ? 1024 : nblk(n, 256);
     hipStream_t st = (hipStream_t)stream;
@@ -2018,38 +2003,38 @@ int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_ou
     case DM_POW_Q4G: k_pow_variant<DM_POW_Q4G><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     case DM_POW_KG: k_pow_variant<DM_POW_KG><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     case DM_POW_FULL: k_pow_variant<DM_POW_FULL><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
-    default: return fail(DM_ERR_ARG, "unknown pow14 variant %d", variant);
+    default: return dm_fail(DM_ERR_ARG, "unknown pow14 variant %d", variant);
     }
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_debug_num_tile_f16(const uint8_t *d_patch_taps, const uint8_t *d_window_taps, int32_t ws,
                           float *d_num, void *stream)
 {
-    if (!d_patch_taps || !d_window_taps || !d_num) return fail(DM_ERR_ARG, "null taps / output");
+    if (!d_patch_taps || !d_window_taps || !d_num) return dm_fail(DM_ERR_ARG, "null taps / output");
     // n + 4 K slots of the 32: ws <= 5 (num_tile_f16 in dm_mfma.h)
-    if (ws != 1 && ws != 3 && ws != 5) return fail(DM_ERR_UNSUPPORTED, "window side %d: the f16 num tile takes 1, 3 or 5", ws);
+    if (ws != 1 && ws != 3 && ws != 5) return dm_fail(DM_ERR_UNSUPPORTED, "window side %d: the f16 num tile takes 1, 3 or 5", ws);
     k_debug_num_tile_f16<<<1, 64, 0, (hipStream_t)stream>>>(d_patch_taps, d_window_taps, ws, d_num);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_rectify64(const double *d_in, size_t n, double *d_out, void *stream)
 {
-    if (!d_in || !d_out) return fail(DM_ERR_ARG, "null pointer");
+    if (!d_in || !d_out) return dm_fail(DM_ERR_ARG, "null pointer");
     if (n == 0) return DM_OK;
     k_rectify<double><<<nblk(n, 256) > 8192 ? 8192 : nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_in, n, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_aggregate(const double *d_in, int32_t T, int32_t h, int32_t w, int32_t rectify, double *d_out,
                  void *stream)
 {
-    if (!d_in || !d_out || T < 1 || h < 1 || w < 1) return fail(DM_ERR_ARG, "bad aggregate arguments");
+    if (!d_in || !d_out || T < 1 || h < 1 || w < 1) return dm_fail(DM_ERR_ARG, "bad aggregate arguments");
     if ((h & 1) || (w & 1))
-        return fail(DM_ERR_SHAPE, "could not broadcast: map side %d must halve (Correlation_map.py:96-103)", (h & 1) ? h : w);
+        return dm_fail(DM_ERR_SHAPE, "could not broadcast: map side %d must halve (Correlation_map.py:96-103)", (h & 1) ? h : w);
     const int W2 = w / 2, h2 = h / 2;
     const char *ag = getenv("DM_AGGREGATE");
     if (W2 >= 16 && 4 * W2 <= 256 && !(ag && ag[0] == '0')) { // streaming kernel
@@ -2062,13 +2047,13 @@ int dm_aggregate(const double *d_in, int32_t T, int32_t h, int32_t w, int32_t re
             const size_t lds = (size_t)4 * BR * W2 * sizeof(double);
             if (vec) k_aggregate_rows<true><<<(unsigned)nwg, 4 * W2, lds, (hipStream_t)stream>>>(d_in, T, h, w, BR, rectify, d_out);
             else k_aggregate_rows<false><<<(unsigned)nwg, 4 * W2, lds, (hipStream_t)stream>>>(d_in, T, h, w, BR, rectify, d_out);
-            HIP_TRY(hipGetLastError());
+            DM_HIP_TRY(hipGetLastError());
             return DM_OK;
         }
     }
     const size_t n = (size_t)T * (h / 2) * (w / 2) * (h / 2) * (w / 2);
     k_aggregate<<<nblk(n, 256) > 65536 ? 65536 : nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_in, T, h, w, rectify, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -2076,26 +2061,26 @@ int dm_match(const dm_tiles *b, const void *d_stats, const double *const *d_leve
              int32_t T, int32_t h0, int32_t w0, int32_t sub_pix, int32_t filter_window,
              int32_t filter_num, int32_t filter_mode, double *d_scratch, double *d_out, void *stream)
 {
-    if (!d_levels || !d_scratch || !d_out) return fail(DM_ERR_ARG, "null pointer");
-    if (T < 1 || h0 < 1 || w0 < 1) return fail(DM_ERR_ARG, "empty batch (T=%d, h0=%d, w0=%d)", T, h0, w0);
-    if (nlev < 2) return fail(DM_ERR_SHAPE, "list index out of range: Matching._B needs >= 2 levels (got %d)", nlev);
-    if (nlev > 31) return fail(DM_ERR_ARG, "too many levels %d", nlev);
+    if (!d_levels || !d_scratch || !d_out) return dm_fail(DM_ERR_ARG, "null pointer");
+    if (T < 1 || h0 < 1 || w0 < 1) return dm_fail(DM_ERR_ARG, "empty batch (T=%d, h0=%d, w0=%d)", T, h0, w0);
+    if (nlev < 2) return dm_fail(DM_ERR_SHAPE, "list index out of range: Matching._B needs >= 2 levels (got %d)", nlev);
+    if (nlev > 31) return dm_fail(DM_ERR_ARG, "too many levels %d", nlev);
     const int K = nlev - 1;
     if ((h0 >> K) << K != h0 || (w0 >> K) << K != w0)
-        return fail(DM_ERR_SHAPE, "map sides %dx%d not divisible by 2^(nlev-1) (nlev=%d)", h0, w0, nlev);
+        return dm_fail(DM_ERR_SHAPE, "map sides %dx%d not divisible by 2^(nlev-1) (nlev=%d)", h0, w0, nlev);
     for (int l = 1; l < nlev; ++l) // level 1 may be on demand too (dm_corr_level12), below the top
         if (!d_levels[l] && !(l == 1 && nlev >= 3 && !d_levels[0]))
-            return fail(DM_ERR_ARG, "null level pointer %d", l);
+            return dm_fail(DM_ERR_ARG, "null level pointer %d", l);
     if (filter_num > 0 && (filter_window < 1 || filter_window > 7))
-        return fail(DM_ERR_UNSUPPORTED, "filter_window_size %d not in [1, 7]", filter_window);
-    if (filter_mode != 0 && filter_mode != 1) return fail(DM_ERR_ARG, "invalid filtering mode %d", filter_mode);
+        return dm_fail(DM_ERR_UNSUPPORTED, "filter_window_size %d not in [1, 7]", filter_window);
+    if (filter_mode != 0 && filter_mode != 1) return dm_fail(DM_ERR_ARG, "invalid filtering mode %d", filter_mode);
     Geo g{};
     Stats s{};
     if (!d_levels[0]) {
         int rc = check_tiles(b);
         if (rc) return rc;
-        if (!d_stats) return fail(DM_ERR_ARG, "level 0 on demand needs the statistics workspace");
-        if (b->T != T || b->h0 != h0 || b->w0 != w0) return fail(DM_ERR_ARG, "tile batch does not match T/h0/w0");
+        if (!d_stats) return dm_fail(DM_ERR_ARG, "level 0 on demand needs the statistics workspace");
+        if (b->T != T || b->h0 != h0 || b->w0 != w0) return dm_fail(DM_ERR_ARG, "tile batch does not match T/h0/w0");
         g = make_geo(b);
         s = stats_view((void *)d_stats, T, h0 * w0);
     }
@@ -2120,9 +2105,9 @@ int dm_match(const dm_tiles *b, const void *d_stats, const double *const *d_leve
     auto filt = [&](int hh, int ww) -> int { // Matching._filter hook (:91-93, :136-138)
         if (fleft > 0) {
             if (hh >= filter_window && ww >= filter_window) {
-                if (hh != ww) return fail(DM_ERR_UNSUPPORTED, "Matching._filter needs square maps (%dx%d): Matching.py:235-236", hh, ww);
+                if (hh != ww) return dm_fail(DM_ERR_UNSUPPORTED, "Matching._filter needs square maps (%dx%d): Matching.py:235-236", hh, ww);
                 k_filter<<<nblk((size_t)T * hh * ww, 64), 64, 0, st>>>(buf[cur], buf[cur ^ 1], T, hh, ww, filter_window, filter_mode);
-                HIP_TRY(hipGetLastError());
+                DM_HIP_TRY(hipGetLastError());
                 cur ^= 1;
             }
             --fleft; // decremented even when the size check skips the filter
@@ -2130,7 +2115,7 @@ int dm_match(const dm_tiles *b, const void *d_stats, const double *const *d_leve
         return DM_OK;
     };
     k_match_top<<<nblk((size_t)T * h * w, 64), 64, 0, st>>>(d_levels[K], T, h, w, buf[cur]);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     int rc = filt(h, w);
     if (rc) return rc;
     for (int l = K - 1; l >= 0; --l) {
@@ -2164,7 +2149,7 @@ int dm_match(const dm_tiles *b, const void *d_stats, const double *const *d_leve
         } else {
             k_match_step<<<nblk(n, 64), 64, 0, st>>>(g, s, d_levels[l], l, T, h, w, buf[cur], buf[cur ^ 1]);
         }
-        HIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         cur ^= 1;
         h *= 2; w *= 2;
         rc = filt(h, w);
@@ -2186,23 +2171,23 @@ int dm_match(const dm_tiles *b, const void *d_stats, const double *const *d_leve
         } else {
             k_subpix<<<nblk((size_t)T * h0 * w0, 64), 64, 0, st>>>(g, s, d_levels[0], T, h0, w0, h0, w0, buf[cur]);
         }
-        HIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
     }
     if (buf[cur] != d_out) // (the parity above makes this unreachable; kept as a guard)
-        HIP_TRY(hipMemcpyAsync(d_out, buf[cur], sizeof(double) * 3 * (size_t)T * h0 * w0, hipMemcpyDeviceToDevice, st));
+        DM_HIP_TRY(hipMemcpyAsync(d_out, buf[cur], sizeof(double) * 3 * (size_t)T * h0 * w0, hipMemcpyDeviceToDevice, st));
     return DM_OK;
 }
 
 int dm_subpix_map(const double *d_level0, int32_t T, int32_t h0, int32_t w0, int32_t hm, int32_t wm,
                   double *d_map, void *stream)
 {
-    if (!d_level0 || !d_map) return fail(DM_ERR_ARG, "dm_subpix_map needs level 0 and the map");
+    if (!d_level0 || !d_map) return dm_fail(DM_ERR_ARG, "dm_subpix_map needs level 0 and the map");
     if (T < 1 || h0 < 1 || w0 < 1 || hm < 1 || wm < 1 || hm > h0 || wm > w0)
-        return fail(DM_ERR_ARG, "dm_subpix_map: T=%d level 0 %dx%d map %dx%d", T, h0, w0, hm, wm);
+        return dm_fail(DM_ERR_ARG, "dm_subpix_map: T=%d level 0 %dx%d map %dx%d", T, h0, w0, hm, wm);
     const Geo g{};
     const Stats s{};
     k_subpix<<<nblk((size_t)T * hm * wm, 64), 64, 0, (hipStream_t)stream>>>(g, s, d_level0, T, h0, w0, hm, wm, d_map);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -2210,34 +2195,34 @@ int dm_subpix_map_tiles(const dm_tiles *b, const void *d_stats, int32_t hm, int3
 {
     int rc = check_tiles(b);
     if (rc) return rc;
-    if (!d_stats || !d_map) return fail(DM_ERR_ARG, "dm_subpix_map_tiles needs the statistics workspace and the map");
+    if (!d_stats || !d_map) return dm_fail(DM_ERR_ARG, "dm_subpix_map_tiles needs the statistics workspace and the map");
     if (hm < 1 || wm < 1 || hm > b->h0 || wm > b->w0)
-        return fail(DM_ERR_ARG, "dm_subpix_map_tiles: map %dx%d for level 0 %dx%d", hm, wm, b->h0, b->w0);
+        return dm_fail(DM_ERR_ARG, "dm_subpix_map_tiles: map %dx%d for level 0 %dx%d", hm, wm, b->h0, b->w0);
     const Geo g = make_geo(b);
     const Stats s = stats_view((void *)d_stats, b->T, b->h0 * b->w0);
     k_subpix<<<nblk((size_t)b->T * hm * wm, 64), 64, 0, (hipStream_t)stream>>>(g, s, nullptr, b->T, b->h0, b->w0, hm, wm, d_map);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_sub_pix_cal(const double *d_arr, const double *d_score, int32_t h, int32_t w, int32_t direction,
                    double ratio, double *d_out, void *stream)
 {
-    if (!d_arr || !d_score || !d_out || h < 1 || w < 1) return fail(DM_ERR_ARG, "bad sub_pix_cal arguments");
-    if (direction != 0 && direction != 1) return fail(DM_ERR_ARG, "direction must be 0 or 1 (got %d)", direction);
+    if (!d_arr || !d_score || !d_out || h < 1 || w < 1) return dm_fail(DM_ERR_ARG, "bad sub_pix_cal arguments");
+    if (direction != 0 && direction != 1) return dm_fail(DM_ERR_ARG, "direction must be 0 or 1 (got %d)", direction);
     const size_t n = (size_t)h * w;
     k_sub_pix_cal<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_arr, d_score, h, w, direction, ratio, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_cal_map(const double *d_map, int32_t T, int32_t h, int32_t w, int32_t mode, double *d_out, void *stream)
 {
-    if (!d_map || !d_out || T < 1 || h < 1 || w < 1) return fail(DM_ERR_ARG, "bad cal_map arguments");
-    if (mode < 0 || mode > 2) return fail(DM_ERR_ARG, "please input valid mode! (%d)", mode);
+    if (!d_map || !d_out || T < 1 || h < 1 || w < 1) return dm_fail(DM_ERR_ARG, "bad cal_map arguments");
+    if (mode < 0 || mode > 2) return dm_fail(DM_ERR_ARG, "please input valid mode! (%d)", mode);
     const size_t n = (size_t)T * h * w;
     k_cal_map<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_map, T, h, w, mode, d_out);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -2247,16 +2232,16 @@ int dm_stitch(const double *d_match, int32_t n0, int32_t n1, int32_t h0, int32_t
 {
     if (!d_match || !d_dmap || !d_score || n0 < 1 || n1 < 1 || stride0 < 1 || stride1 < 1 ||
         nmodes < 0 || nmodes > 8 || (nmodes && !modes))
-        return fail(DM_ERR_ARG, "bad stitch arguments");
+        return dm_fail(DM_ERR_ARG, "bad stitch arguments");
     Modes m;
     for (int k = 0; k < 8; ++k) m.m[k] = k < nmodes ? modes[k] : 0;
     for (int k = 0; k < nmodes; ++k)
-        if (m.m[k] < 0 || m.m[k] > 2) return fail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
+        if (m.m[k] < 0 || m.m[k] > 2) return dm_fail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
     const int Hout = stride0 * (n0 - 1) + h0, Wout = stride1 * (n1 - 1) + w0;
     const size_t n = (size_t)Hout * Wout;
     k_stitch<<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(d_match, n0, n1, h0, w0, stride0, stride1, m,
                                                             nmodes, d_dmap, d_score, Hout, Wout);
-    HIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

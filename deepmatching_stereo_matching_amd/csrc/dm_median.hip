@@ -51,38 +51,12 @@
 // input's bits there for d_changed: a thread reads its own cell of d_in before it writes it.
 #include <hip/hip_runtime.h>
 
-#include <float.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/dmstereo.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int mfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define MHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return mfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY, dm_is_hole, dm_maps_plan, dm_tile_env
 
 #define MED_THREADS 256
 #define MED_RMAX 7
 #define MED_SENT 0xffffffffffffffffULL      // key of an unusable tap
 #define MED_SIGN 0x8000000000000000ULL
-
-// the range test on the double itself: NaN and +-inf fail it (dm_fill.hip: fill_is_hole)
-__device__ __forceinline__ bool med_is_hole(double x) { return !(x >= -DBL_MAX && x <= DBL_MAX); }
 
 __device__ __forceinline__ uint64_t med_key(double x)
 {
@@ -219,7 +193,7 @@ __global__ __launch_bounds__(MED_THREADS) void k_median(const double *in, const 
         const bool inside = y >= 0 && y < H && x >= 0 && x < W;
         const size_t c = inside ? (size_t)y * W + x : 0;
         const double v = in[c];
-        bool usable = inside && !med_is_hole(v);
+        bool usable = inside && !dm_is_hole(v);
         if (WT) {
             const double w = weight[c];
             usable = usable && w > 0.0 && w <= DBL_MAX;         // (a NaN weight fails both)
@@ -236,7 +210,7 @@ __global__ __launch_bounds__(MED_THREADS) void k_median(const double *in, const 
         const size_t c = (size_t)y * W + x;
         const double xc = in[c];
         double res = xc;
-        if (!med_is_hole(xc) || fill) {
+        if (!dm_is_hole(xc) || fill) {
             const int ctr = (ty + r) * LW + tx + r;
             uint64_t key;
             bool found;
@@ -261,8 +235,7 @@ __global__ __launch_bounds__(MED_THREADS) void k_median(const double *in, const 
 // false for a shape the entry does not take (the limits of dm_fill_bytes)
 static bool med_plan(int32_t M, int32_t H, int32_t W, size_t *plane)
 {
-    if (M < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return false;
-    if (M > 65535 || H > 64 * 65535 || W > 64 * 65535) return false;
+    if (!dm_maps_plan(M, H, W, 64 * 65535)) return false;
     *plane = ((size_t)M * H * W * sizeof(double) + 15) & ~(size_t)15;
     return true;
 }
@@ -275,12 +248,7 @@ static bool med_plan(int32_t M, int32_t H, int32_t W, size_t *plane)
 // one, for measurements and tests.
 static int med_tile_shift(int32_t M, int32_t H, int32_t W, int r)
 {
-    const char *e = getenv("DM_MEDIAN_TILE");
-    if (e && *e) {
-        const int v = atoi(e);
-        if (v == 16) return 4;
-        if (v == 32) return 5;
-    }
+    if (const int ts = dm_tile_env("DM_MEDIAN_TILE")) return ts;
     const long long tiles = (long long)((H + 31) >> 5) * ((W + 31) >> 5) * M;
     return r <= 2 && tiles >= 4096 ? 5 : 4;
 }
@@ -310,18 +278,18 @@ int dm_median_filter(const double *d_in, const double *d_weight, int32_t weight_
                      int32_t W, int32_t radius, int32_t min_count, int32_t iters, int32_t flags, double *d_out,
                      uint8_t *d_changed, void *d_work, void *stream)
 {
-    if (!d_in || !d_out || !d_work) return mfail(DM_ERR_ARG, "null input / output / workspace pointer");
-    if (M < 1 || H < 1 || W < 1) return mfail(DM_ERR_ARG, "bad median shape M=%d H=%d W=%d", M, H, W);
-    if (radius < 1 || radius > MED_RMAX) return mfail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", MED_RMAX, radius);
-    if (iters < 1 || iters > 64) return mfail(DM_ERR_ARG, "iters must be in [1, 64] (got %d)", iters);
+    if (!d_in || !d_out || !d_work) return dm_fail(DM_ERR_ARG, "null input / output / workspace pointer");
+    if (M < 1 || H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad median shape M=%d H=%d W=%d", M, H, W);
+    if (radius < 1 || radius > MED_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", MED_RMAX, radius);
+    if (iters < 1 || iters > 64) return dm_fail(DM_ERR_ARG, "iters must be in [1, 64] (got %d)", iters);
     const int K = (2 * radius + 1) * (2 * radius + 1);
-    if (min_count < 1 || min_count > K) return mfail(DM_ERR_ARG, "min_count must be in [1, %d] (got %d)", K, min_count);
-    if (flags & ~DM_MEDIAN_FILL) return mfail(DM_ERR_ARG, "unknown flags 0x%x", flags);
+    if (min_count < 1 || min_count > K) return dm_fail(DM_ERR_ARG, "min_count must be in [1, %d] (got %d)", K, min_count);
+    if (flags & ~DM_MEDIAN_FILL) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     if (d_weight && weight_maps != 1 && weight_maps != M)
-        return mfail(DM_ERR_ARG, "weight_maps must be 1 or M=%d (got %d)", M, weight_maps);
+        return dm_fail(DM_ERR_ARG, "weight_maps must be 1 or M=%d (got %d)", M, weight_maps);
     size_t plane;
     if (!med_plan(M, H, W, &plane))
-        return mfail(DM_ERR_UNSUPPORTED,
+        return dm_fail(DM_ERR_UNSUPPORTED,
                      "median filter of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)", M, H, W);
     hipStream_t st = (hipStream_t)stream;
     const int wt = d_weight ? 1 : 0;
@@ -331,7 +299,7 @@ int dm_median_filter(const double *d_in, const double *d_weight, int32_t weight_
     const bool inplace = d_in == d_out;
     const double *src = d_in;
     if (inplace && iters == 1) {      // the pass would read what it writes
-        MHIP_TRY(hipMemcpyAsync(work0, d_in, (size_t)M * H * W * sizeof(double), hipMemcpyDeviceToDevice, st));
+        DM_HIP_TRY(hipMemcpyAsync(work0, d_in, (size_t)M * H * W * sizeof(double), hipMemcpyDeviceToDevice, st));
         src = work0;
     }
     const double *orig = src;         // holds the input's bits until the last pass has read them
@@ -356,7 +324,7 @@ int dm_median_filter(const double *d_in, const double *d_weight, int32_t weight_
             else MED_GO(0, 0);
         }
 #undef MED_GO
-        MHIP_TRY(e);
+        DM_HIP_TRY(e);
         src = dst;
     }
     return DM_OK;

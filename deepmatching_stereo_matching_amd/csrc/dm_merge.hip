@@ -19,29 +19,9 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
 
-#include "../../include/dmstereo.h"
 #include "dm_fb_err.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int mfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define MHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return mfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY
 
 struct MergeModes {
     int m[8];
@@ -255,33 +235,33 @@ int dm_stitch_merge(const double *d_fwd, const double *d_bwd, int32_t n0, int32_
 {
     if (!d_fwd || !d_dmap || !d_score || n0 < 1 || n1 < 1 || h0 < 1 || w0 < 1 || stride0 < 1 || stride1 < 1 ||
         nmodes < 0 || nmodes > 8 || (nmodes && !modes))
-        return mfail(DM_ERR_ARG, "bad stitch arguments");
+        return dm_fail(DM_ERR_ARG, "bad stitch arguments");
     MergeModes m;
     MergeGeom g;
     g.used = 0;
     for (int k = 0; k < 8; ++k) m.m[k] = k < nmodes ? modes[k] : 0;
     for (int k = 0; k < nmodes; ++k) {
-        if (m.m[k] < 0 || m.m[k] > 2) return mfail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
+        if (m.m[k] < 0 || m.m[k] > 2) return dm_fail(DM_ERR_ARG, "please input valid mode! (%d)", m.m[k]);
         g.used |= 1u << m.m[k];
     }
     if (rule < DM_MERGE_LAST || rule > DM_MERGE_MEDIAN)
-        return mfail(DM_ERR_ARG, "merge rule must be 0..3 (got %d)", rule);
+        return dm_fail(DM_ERR_ARG, "merge rule must be 0..3 (got %d)", rule);
     if (min_count < 1 || min_count > 255)
-        return mfail(DM_ERR_ARG, "min_count must be in [1, 255] (got %d)", min_count);
+        return dm_fail(DM_ERR_ARG, "min_count must be in [1, 255] (got %d)", min_count);
     if (rule == DM_MERGE_LAST && min_count != 1)
-        return mfail(DM_ERR_ARG, "min_count must be 1 with the rule DM_MERGE_LAST (got %d)", min_count);
-    if (d_err && !d_bwd) return mfail(DM_ERR_ARG, "an err output needs the backward tiles");
-    if (d_bwd && !(tol >= 0.0)) return mfail(DM_ERR_ARG, "tolerance must be >= 0 (got %g)", tol);
+        return dm_fail(DM_ERR_ARG, "min_count must be 1 with the rule DM_MERGE_LAST (got %d)", min_count);
+    if (d_err && !d_bwd) return dm_fail(DM_ERR_ARG, "an err output needs the backward tiles");
+    if (d_bwd && !(tol >= 0.0)) return dm_fail(DM_ERR_ARG, "tolerance must be >= 0 (got %g)", tol);
     const long long Hout = (long long)stride0 * (n0 - 1) + h0, Wout = (long long)stride1 * (n1 - 1) + w0;
     if (Hout > 0x7fffffffLL || Wout > 0x7fffffffLL)
-        return mfail(DM_ERR_UNSUPPORTED, "stitched map of %lld x %lld cells", Hout, Wout);
+        return dm_fail(DM_ERR_UNSUPPORTED, "stitched map of %lld x %lld cells", Hout, Wout);
     const unsigned long long cells = (unsigned long long)Hout * (unsigned long long)Wout;
     const unsigned long long nb = (cells + 255) / 256;
-    if (nb > 0x7fffffffull) return mfail(DM_ERR_UNSUPPORTED, "map of %llu cells", cells);
+    if (nb > 0x7fffffffull) return dm_fail(DM_ERR_UNSUPPORTED, "map of %llu cells", cells);
     const long long c0 = ceil_div(h0, stride0), c1 = ceil_div(w0, stride1);
     const long long cand = (n0 < c0 ? n0 : c0) * (n1 < c1 ? n1 : c1);
     if (cand > DM_MERGE_MAX_CAND)
-        return mfail(DM_ERR_UNSUPPORTED, "up to %lld tiles cover one pixel, the merge takes %d", cand,
+        return dm_fail(DM_ERR_UNSUPPORTED, "up to %lld tiles cover one pixel, the merge takes %d", cand,
                      DM_MERGE_MAX_CAND);
     g.n0 = n0, g.n1 = n1, g.h0 = h0, g.w0 = w0, g.s0 = stride0, g.s1 = stride1;
     g.Hout = (int)Hout, g.Wout = (int)Wout;
@@ -303,7 +283,7 @@ int dm_stitch_merge(const double *d_fwd, const double *d_bwd, int32_t n0, int32_
         merge_launch<DM_MERGE_MEDIAN>(fb, (unsigned)nb, st, d_fwd, d_bwd, g, m, d_dmap, d_score, d_err, d_spread, d_count);
         break;
     }
-    MHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

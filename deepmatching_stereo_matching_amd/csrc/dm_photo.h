@@ -4,18 +4,14 @@
 #ifndef DM_PHOTO_H
 #define DM_PHOTO_H
 
-#include <hip/hip_runtime.h>
-
-#include <float.h>
-#include <stdint.h>
+#include "dm_host.h"      // dm_is_hole; dm_fail and dm_maps_plan for the two entries
 
 #define PHO_TX 32
 #define PHO_TY 8
 #define PHO_RMAX 7
 #define PHO_OFFMAX (1 << 30)
 
-// the range test on the double itself: NaN and +-inf fail it (dm_fill.hip: fill_is_hole)
-__device__ __forceinline__ bool pho_finite(double x) { return x >= -DBL_MAX && x <= DBL_MAX; }
+__device__ __forceinline__ bool pho_finite(double x) { return !dm_is_hole(x); }
 
 __device__ __forceinline__ uint32_t pho_ld4(const uint8_t *p)      // a dword at any byte address
 {

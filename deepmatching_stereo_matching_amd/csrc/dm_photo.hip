@@ -34,24 +34,9 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "../../include/dmstereo.h"
 #include "dm_photo.h"      // PHO_*, pho_finite, pho_row, pho_dot, pho_sum: shared with dm_photo_refine.hip
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int pfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
 
 // grid: tiles_x * tiles_y workgroups of PHO_TX x PHO_TY cells.  ND = (r + 2) / 2 dwords per row.
 template <int ND>
@@ -180,12 +165,7 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_photo(const uint8_t *img1, s
 
 // ---- host side ------------------------------------------------------------------------------
 // false for a shape the entry does not take (the limits of dm_median_bytes)
-static bool pho_plan(int32_t M, int32_t H, int32_t W)
-{
-    if (M < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return false;
-    if (M > 65535 || H > 64 * 65535 || W > 64 * 65535) return false;
-    return true;
-}
+static bool pho_plan(int32_t M, int32_t H, int32_t W) { return dm_maps_plan(M, H, W, 64 * 65535); }
 
 extern "C" {
 
@@ -197,29 +177,29 @@ int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2
                    double *d_score, double *d_warped, uint8_t *d_rejected, void *d_work, void *stream)
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_work)
-        return pfail(DM_ERR_ARG, "null image / disparity / workspace pointer");
-    if (Hi < 1 || Wi < 1) return pfail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
+        return dm_fail(DM_ERR_ARG, "null image / disparity / workspace pointer");
+    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
     if (stride1 < Wi || stride2 < Wi)
-        return pfail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
+        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
                      (long long)stride2);
-    if (H < 1 || W < 1) return pfail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
+    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
     if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return pfail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return pfail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
-    if (flags & ~DM_PHOTO_REJECT) return pfail(DM_ERR_ARG, "unknown flags 0x%x", flags);
+        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
+    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (flags & ~DM_PHOTO_REJECT) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     const int reject = (flags & DM_PHOTO_REJECT) ? 1 : 0;
     if (reject) {
-        if (!d_maps) return pfail(DM_ERR_ARG, "DM_PHOTO_REJECT needs d_maps");
-        if (M < 1) return pfail(DM_ERR_ARG, "bad map count M=%d", M);
+        if (!d_maps) return dm_fail(DM_ERR_ARG, "DM_PHOTO_REJECT needs d_maps");
+        if (M < 1) return dm_fail(DM_ERR_ARG, "bad map count M=%d", M);
         if (!(min_score >= -1.0 && min_score <= 1.0))
-            return pfail(DM_ERR_ARG, "min_score must be in [-1, 1] (got %g)", min_score);
+            return dm_fail(DM_ERR_ARG, "min_score must be in [-1, 1] (got %g)", min_score);
     } else {
-        if (d_rejected) return pfail(DM_ERR_ARG, "d_rejected needs DM_PHOTO_REJECT");
-        if (!d_score && !d_warped) return pfail(DM_ERR_ARG, "no output: d_score and d_warped are null");
+        if (d_rejected) return dm_fail(DM_ERR_ARG, "d_rejected needs DM_PHOTO_REJECT");
+        if (!d_score && !d_warped) return dm_fail(DM_ERR_ARG, "no output: d_score and d_warped are null");
         M = 1;      // (d_maps and M are not read)
     }
     if (!pho_plan(M, H, W))
-        return pfail(DM_ERR_UNSUPPORTED,
+        return dm_fail(DM_ERR_UNSUPPORTED,
                      "photo score of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)", M, H, W);
     const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
     const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
@@ -235,8 +215,7 @@ int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2
     default: PHO_GO(4); break;
     }
 #undef PHO_GO
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e), (int)e);
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

@@ -25,24 +25,9 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
 #include <string.h>
 
-#include "../../include/dmstereo.h"
 #include "dm_photo.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int rfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
 
 #define REF_SMAX 3
 #define REF_POSMAX 1073741824.0      // 2^30
@@ -312,20 +297,20 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
                     double *d_out_row, double *d_out_col, double *d_score, int8_t *d_shift, void *d_work, void *stream)
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_out_row || !d_out_col || !d_work)
-        return rfail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
-    if (Hi < 1 || Wi < 1) return rfail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
+        return dm_fail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
+    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
     if (stride1 < Wi || stride2 < Wi)
-        return rfail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
+        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
                      (long long)stride2);
-    if (H < 1 || W < 1) return rfail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
+    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
     if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return rfail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return rfail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
-    if (search < 1 || search > REF_SMAX) return rfail(DM_ERR_ARG, "search must be in [1, %d] (got %d)", REF_SMAX, search);
-    if (!(min_gain >= 0.0 && min_gain <= 2.0)) return rfail(DM_ERR_ARG, "min_gain must be in [0, 2] (got %g)", min_gain);
-    if (flags & ~DM_REFINE_SUBPIX) return rfail(DM_ERR_ARG, "unknown flags 0x%x", flags);
+        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
+    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (search < 1 || search > REF_SMAX) return dm_fail(DM_ERR_ARG, "search must be in [1, %d] (got %d)", REF_SMAX, search);
+    if (!(min_gain >= 0.0 && min_gain <= 2.0)) return dm_fail(DM_ERR_ARG, "min_gain must be in [0, 2] (got %g)", min_gain);
+    if (flags & ~DM_REFINE_SUBPIX) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     if (!ref_plan(Hi, Wi, H, W, radius, search))
-        return rfail(DM_ERR_UNSUPPORTED,
+        return dm_fail(DM_ERR_UNSUPPORTED,
                      "photo refine of %d x %d cells on a %d x %d image (at most 2^31 - 1 cells, 2^30 pixels a side)", H,
                      W, Hi, Wi);
     const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
@@ -350,8 +335,7 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
     }
 #undef REF_GO_S
 #undef REF_GO
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return rfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e), (int)e);
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

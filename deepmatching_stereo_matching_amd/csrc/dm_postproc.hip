@@ -18,33 +18,13 @@
 #include <hip/hip_runtime.h>
 
 #include <math.h>
-#include <stdarg.h>
 #include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <vector>
 
-#include "../../include/dmstereo.h"
 #include "dm_exp.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int pfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define PHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return pfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY
 
 // python index semantics for the only negative index the loops can form (-1)
 __host__ __device__ __forceinline__ int pyix(int i, int n) { return i < 0 ? i + n : i; }
@@ -451,17 +431,17 @@ static void seq_sum(const double *d, long long n, double *out, hipStream_t st)
 static int check_sweep(int kind, int h, int w, int s0, int s1, int e)
 {
     if (kind != DM_GS_FWD4 && kind != DM_GS_BWD4 && kind != DM_GS_BILAT)
-        return pfail(DM_ERR_ARG, "unknown sweep kind %d", kind);
-    if (h < 1 || w < 1 || e < 0) return pfail(DM_ERR_ARG, "bad map %dx%d / exclusion %d", h, w, e);
+        return dm_fail(DM_ERR_ARG, "unknown sweep kind %d", kind);
+    if (h < 1 || w < 1 || e < 0) return dm_fail(DM_ERR_ARG, "bad map %dx%d / exclusion %d", h, w, e);
     if (s0 > h || s1 > w || s0 < 0 || s1 < 0)
-        return pfail(DM_ERR_SHAPE, "size (%d, %d) exceeds the map (%d, %d)", s0, s1, h, w);
-    if (kind == DM_GS_BILAT && e > 15) return pfail(DM_ERR_UNSUPPORTED, "exclusion %d > 15 not supported", e);
+        return dm_fail(DM_ERR_SHAPE, "size (%d, %d) exceeds the map (%d, %d)", s0, s1, h, w);
+    if (kind == DM_GS_BILAT && e > 15) return dm_fail(DM_ERR_UNSUPPORTED, "exclusion %d > 15 not supported", e);
     const GsGeo g = gs_geo(kind, h, w, s0, s1, e);
     if (gs_count(g) == 0) return DM_OK;
     if (kind != DM_GS_BILAT) {
         // highest row / column any update touches (r + 1, c + 1): python raises IndexError
         const int rmax = kind == DM_GS_FWD4 ? s0 - e - 1 : s0 - e, cmax = kind == DM_GS_FWD4 ? s1 - e - 1 : s1 - e;
-        if (rmax >= h || cmax >= w) return pfail(DM_ERR_SHAPE, "list index out of range (index %d, %d of a %dx%d map)",
+        if (rmax >= h || cmax >= w) return dm_fail(DM_ERR_SHAPE, "list index out of range (index %d, %d of a %dx%d map)",
                                                  rmax, cmax, h, w);
     }
     return DM_OK;
@@ -474,7 +454,7 @@ int dm_gs_schedule(int32_t kind, int32_t h, int32_t w, int32_t s0, int32_t s1, i
 {
     int rc = check_sweep(kind, h, w, s0, s1, excl);
     if (rc) return rc;
-    if (!n_levels) return pfail(DM_ERR_ARG, "null n_levels");
+    if (!n_levels) return dm_fail(DM_ERR_ARG, "null n_levels");
     const GsGeo g = gs_geo(kind, h, w, s0, s1, excl);
     const long long n = gs_count(g);
     *n_levels = 0;
@@ -482,8 +462,8 @@ int dm_gs_schedule(int32_t kind, int32_t h, int32_t w, int32_t s0, int32_t s1, i
         if (level_off) level_off[0] = 0;
         return DM_OK;
     }
-    if (!order || !level_off) return pfail(DM_ERR_ARG, "null order / level_off");
-    if (n > 0x7fffffffLL) return pfail(DM_ERR_UNSUPPORTED, "sweep of %lld updates", n);
+    if (!order || !level_off) return dm_fail(DM_ERR_ARG, "null order / level_off");
+    if (n > 0x7fffffffLL) return dm_fail(DM_ERR_UNSUPPORTED, "sweep of %lld updates", n);
     std::vector<int32_t> lastw((size_t)h * w, -1), maxr((size_t)h * w, -1), lev((size_t)n);
     const int e = excl;
     int cells[4 * 31 * 31 + 8];
@@ -526,9 +506,9 @@ int dm_gs_schedule(int32_t kind, int32_t h, int32_t w, int32_t s0, int32_t s1, i
 int dm_image_threshold(const double *d_in, size_t n, double lo, double hi, double *d_out, void *stream)
 {
     if (n == 0) return DM_OK;
-    if (!d_in || !d_out) return pfail(DM_ERR_ARG, "null pointer");
+    if (!d_in || !d_out) return dm_fail(DM_ERR_ARG, "null pointer");
     k_threshold<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_in, n, lo, hi, d_out);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -541,46 +521,46 @@ int dm_optimize_loop(double *d_img, const double *d_coef, int32_t hc, int32_t wc
     if (rc) return rc;
     rc = check_sweep(DM_GS_BWD4, h, w, s0, s1, excl);
     if (rc) return rc;
-    if (!d_img || !d_error) return pfail(DM_ERR_ARG, "null image / error pointer");
+    if (!d_img || !d_error) return dm_fail(DM_ERR_ARG, "null image / error pointer");
     const GsGeo gf = gs_geo(DM_GS_FWD4, h, w, s0, s1, excl), gb = gs_geo(DM_GS_BWD4, h, w, s0, s1, excl);
     const long long n = gs_count(gf);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        PHIP_TRY(hipMemsetAsync(d_error, 0, sizeof(double), st));
+        DM_HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(double), st));
         return DM_OK;
     }
     // coefficient[i, j] for every updated cell (rows <= s0-1-e, cols <= s1-1-e)
     if (!d_coef || hc < s0 - excl || wc < s1 - excl)
-        return pfail(DM_ERR_SHAPE, "coefficient %dx%d does not cover the sweep (size %d, %d, exclusion %d)", hc, wc,
+        return dm_fail(DM_ERR_SHAPE, "coefficient %dx%d does not cover the sweep (size %d, %d, exclusion %d)", hc, wc,
                      s0, s1, excl);
     if (!d_fwd_order || !d_fwd_off || !d_bwd_order || !d_bwd_off || !d_diff || fwd_levels < 1 || bwd_levels < 1)
-        return pfail(DM_ERR_ARG, "missing schedule / diff buffer");
+        return dm_fail(DM_ERR_ARG, "missing schedule / diff buffer");
     if (gs_pf())
         k_optimize_loop_pf<<<1, 1024, 0, st>>>(d_img, d_coef, wc, alpha, gf, d_fwd_order, d_fwd_off, fwd_levels, gb,
                                                d_bwd_order, d_bwd_off, bwd_levels, d_diff);
     else
         k_optimize_loop<<<1, 1024, 0, st>>>(d_img, d_coef, wc, alpha, gf, d_fwd_order, d_fwd_off, fwd_levels, gb,
                                             d_bwd_order, d_bwd_off, bwd_levels, d_diff);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     seq_sum(d_diff, n, d_error, st);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_make_weight(const double *d_guide, int32_t h, int32_t w, int32_t s0, int32_t s1, int32_t excl,
                    double den_color, double den_space, double *d_gauss, double *d_color, void *stream)
 {
-    if (!d_gauss || !d_color || (!d_guide && s0 > 0)) return pfail(DM_ERR_ARG, "null pointer");
-    if (excl < 0 || excl > 15) return pfail(DM_ERR_UNSUPPORTED, "exclusion %d outside 0..15", excl);
-    if (s0 > h || s1 > w) return pfail(DM_ERR_SHAPE, "size (%d, %d) exceeds the guide (%d, %d)", s0, s1, h, w);
+    if (!d_gauss || !d_color || (!d_guide && s0 > 0)) return dm_fail(DM_ERR_ARG, "null pointer");
+    if (excl < 0 || excl > 15) return dm_fail(DM_ERR_UNSUPPORTED, "exclusion %d outside 0..15", excl);
+    if (s0 > h || s1 > w) return dm_fail(DM_ERR_SHAPE, "size (%d, %d) exceeds the guide (%d, %d)", s0, s1, h, w);
     if (s0 - excl < 0 || s1 - excl < 0)
-        return pfail(DM_ERR_SHAPE, "negative dimensions are not allowed (size %d, %d, exclusion %d)", s0, s1, excl);
+        return dm_fail(DM_ERR_SHAPE, "negative dimensions are not allowed (size %d, %d, exclusion %d)", s0, s1, excl);
     const int W = 2 * excl + 1;
     const size_t total = (size_t)(s0 - excl) * (s1 - excl) * W * W;
     const size_t work = total > (size_t)W * W ? total : (size_t)W * W;
     k_make_weight<<<(unsigned)((work + 255) / 256), 256, 0, (hipStream_t)stream>>>(d_guide, w, s0, s1, excl, den_color,
                                                                                   den_space, d_gauss, d_color);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
@@ -591,19 +571,19 @@ int dm_opt_loop_bilateral(double *d_img, const double *d_color, const double *d_
 {
     int rc = check_sweep(DM_GS_BILAT, h, w, s0, s1, excl);
     if (rc) return rc;
-    if (!d_img || !d_error) return pfail(DM_ERR_ARG, "null image / error pointer");
+    if (!d_img || !d_error) return dm_fail(DM_ERR_ARG, "null image / error pointer");
     const GsGeo g = gs_geo(DM_GS_BILAT, h, w, s0, s1, excl);
     const long long n = gs_count(g);
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        PHIP_TRY(hipMemsetAsync(d_error, 0, sizeof(double), st));
+        DM_HIP_TRY(hipMemsetAsync(d_error, 0, sizeof(double), st));
         return DM_OK;
     }
     // coefficient[e, e], [e, e +- 1] / [e +- 1, e] with python's -1 wrap
     if (!d_coef || hc < 1 || wc < 1 || excl >= hc || excl >= wc || (vertical ? excl + 1 >= hc : excl + 1 >= wc))
-        return pfail(DM_ERR_SHAPE, "index %d is out of bounds for the %dx%d coefficient", excl + 1, hc, wc);
+        return dm_fail(DM_ERR_SHAPE, "index %d is out of bounds for the %dx%d coefficient", excl + 1, hc, wc);
     if (!d_color || !d_gauss || !d_order || !d_off || !d_diff || n_levels < 1)
-        return pfail(DM_ERR_ARG, "missing weights / schedule / diff buffer");
+        return dm_fail(DM_ERR_ARG, "missing weights / schedule / diff buffer");
     const int vt = vertical ? 1 : 0;
 #define DM_BILAT_PF(E_, LPU_, R_, NT_)                                                                            \
     k_bilateral_pf<E_, LPU_, R_, NT_><<<1, NT_, 0, st>>>(d_img, d_color, d_gauss, d_coef, hc, wc, vt, g, d_order, d_off,  \
@@ -620,22 +600,22 @@ int dm_opt_loop_bilateral(double *d_img, const double *d_color, const double *d_
         k_bilateral<<<1, 1024, 0, st>>>(d_img, d_color, d_gauss, d_coef, hc, wc, vt, g, d_order, d_off, n_levels,
                                         d_diff);
 #undef DM_BILAT_PF
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     seq_sum(d_diff, n, d_error, st);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 
 int dm_seq_sum(const double *d_v, int64_t n, double *d_out, void *stream)
 {
-    if (n < 0 || (n > 0 && !d_v) || !d_out) return pfail(DM_ERR_ARG, "bad sequence sum arguments");
+    if (n < 0 || (n > 0 && !d_v) || !d_out) return dm_fail(DM_ERR_ARG, "bad sequence sum arguments");
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) {
-        PHIP_TRY(hipMemsetAsync(d_out, 0, sizeof(double), st));
+        DM_HIP_TRY(hipMemsetAsync(d_out, 0, sizeof(double), st));
         return DM_OK;
     }
     seq_sum(d_v, (long long)n, d_out, st);
-    PHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

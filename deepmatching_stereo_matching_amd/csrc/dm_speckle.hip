@@ -42,31 +42,9 @@
 // Integer atomics only.
 #include <hip/hip_runtime.h>
 
-#include <float.h>
 #include <math.h>
-#include <stdarg.h>
-#include <stdint.h>
-#include <stdlib.h>
 
-#include "../../include/dmstereo.h"
-
-// error reporting lives in dm_kernels.hip (one thread-local message per thread)
-__attribute__((visibility("hidden"))) int dm_vfail(int code, const char *fmt, va_list ap);
-
-static int sfail(int code, const char *fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    const int r = dm_vfail(code, fmt, ap);
-    va_end(ap);
-    return r;
-}
-
-#define SHIP_TRY(x)                                                                          \
-    do {                                                                                     \
-        hipError_t e_ = (x);                                                                 \
-        if (e_ != hipSuccess) return sfail(DM_ERR_HIP, "HIP error: %s (%d)", hipGetErrorString(e_), (int)e_); \
-    } while (0)
+#include "dm_host.h"      // dm_fail, DM_HIP_TRY, dm_is_hole, dm_nan, dm_maps_plan
 
 #define SPK_TMAX 64                      // largest (and default) tile side; a power of two
 #define SPK_THREADS 256
@@ -76,13 +54,8 @@ static int sfail(int code, const char *fmt, ...)
 static constexpr size_t SPK_LOCAL_LDS = (size_t)SPK_TMAX * SPK_TMAX * (sizeof(double) + sizeof(int));
 static constexpr size_t SPK_ONE_LDS = SPK_LOCAL_LDS + (size_t)SPK_TMAX * SPK_TMAX * sizeof(uint32_t);
 
-// the range test on the double itself: NaN and +-inf fail it (dm_fill.hip: fill_is_hole)
-__device__ __forceinline__ bool spk_is_hole(double x) { return !(x >= -DBL_MAX && x <= DBL_MAX); }
-
 // both finite; a difference that overflows to inf is joined only by max_diff = +inf
 __device__ __forceinline__ bool spk_joined(double a, double b, double max_diff) { return fabs(a - b) <= max_diff; }
-
-__device__ __forceinline__ double spk_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // ---- union-find on the parents of one tile in LDS -------------------------------------------
 __device__ __forceinline__ int spk_lfind(int *P, int a)
@@ -120,7 +93,7 @@ __device__ __forceinline__ void spk_tile_label(const double *in, int H, int W, i
     const int T = 1 << ts, cells = T * T;
     for (int l = threadIdx.x; l < cells; l += SPK_THREADS) {
         const int y = y0 + (l >> ts), x = x0 + (l & (T - 1));
-        const double v = (y < H && x < W) ? in[(size_t)y * W + x] : spk_nan();
+        const double v = (y < H && x < W) ? in[(size_t)y * W + x] : dm_nan();
         V[l] = v;
     }
     __syncthreads();
@@ -131,11 +104,11 @@ __device__ __forceinline__ void spk_tile_label(const double *in, int H, int W, i
     const int lane = threadIdx.x & 63;
     for (int l = threadIdx.x; l < cells; l += SPK_THREADS) {
         const double v = V[l];
-        const bool hole = spk_is_hole(v);
+        const bool hole = dm_is_hole(v);
         bool brk = true;
         if (!hole && (l & (T - 1)) > 0) {
             const double u = V[l - 1];
-            brk = spk_is_hole(u) || !spk_joined(v, u, max_diff);
+            brk = dm_is_hole(u) || !spk_joined(v, u, max_diff);
         }
         const unsigned long long m = __ballot(brk) & ((2ULL << lane) - 1ULL);      // column 0 always breaks: m != 0
         P[l] = hole ? -1 : l - (lane - (63 - __clzll(m)));
@@ -145,10 +118,10 @@ __device__ __forceinline__ void spk_tile_label(const double *in, int H, int W, i
     // to its left does so already (both runs reach one cell further left and are joined there)
     for (int l = threadIdx.x + T; l < cells; l += SPK_THREADS) {
         const double v = V[l], u = V[l - T];
-        if (spk_is_hole(v) || spk_is_hole(u) || !spk_joined(v, u, max_diff)) continue;
+        if (dm_is_hole(v) || dm_is_hole(u) || !spk_joined(v, u, max_diff)) continue;
         if ((l & (T - 1)) > 0) {
             const double vl = V[l - 1], ul = V[l - T - 1];
-            if (!spk_is_hole(vl) && !spk_is_hole(ul) && spk_joined(v, vl, max_diff) && spk_joined(u, ul, max_diff) &&
+            if (!dm_is_hole(vl) && !dm_is_hole(ul) && spk_joined(v, vl, max_diff) && spk_joined(u, ul, max_diff) &&
                 spk_joined(vl, ul, max_diff))
                 continue;
         }
@@ -158,7 +131,7 @@ __device__ __forceinline__ void spk_tile_label(const double *in, int H, int W, i
     // flatten: no union runs any more; a store replaces a parent by one of its ancestors, so a
     // find that reads either value ends at the same root
     for (int l = threadIdx.x; l < cells; l += SPK_THREADS) {
-        if (spk_is_hole(V[l])) continue;
+        if (dm_is_hole(V[l])) continue;
         const int r = spk_lfind(P, l);
         __hip_atomic_store(&P[l], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
@@ -243,13 +216,13 @@ __global__ __launch_bounds__(2 * SPK_TMAX) void k_spk_border(const double *in, i
         return;
     }
     const double va = in[a], vb = in[b];
-    if (spk_is_hole(va) || spk_is_hole(vb) || !spk_joined(va, vb, max_diff)) return;
+    if (dm_is_hole(va) || dm_is_hole(vb) || !spk_joined(va, vb, max_diff)) return;
     if (!first) {
         // the previous pair along the edge does this union already when it is joined itself and
         // joined with this pair on both sides (the two cells of a side share a tile, so
         // k_spk_local left them under one label)
         const double pa = in[a - back], pb = in[b - back];
-        if (!spk_is_hole(pa) && !spk_is_hole(pb) && spk_joined(va, pa, max_diff) && spk_joined(vb, pb, max_diff) &&
+        if (!dm_is_hole(pa) && !dm_is_hole(pb) && spk_joined(va, pa, max_diff) && spk_joined(vb, pb, max_diff) &&
             spk_joined(pa, pb, max_diff))
             return;
     }
@@ -391,8 +364,7 @@ struct SpkPlan {
 // false for a shape the entry does not take
 static bool spk_plan(int32_t M, int32_t H, int32_t W, SpkPlan *p)
 {
-    if (M < 1 || H < 1 || W < 1 || (long long)H * W > 0x7fffffffLL) return false;      // labels are int32
-    if (M > 65535 || H > SPK_TMAX * 65535 || W > SPK_TMAX * 65535) return false;        // grid y / z
+    if (!dm_maps_plan(M, H, W, SPK_TMAX * 65535)) return false;      // labels are int32; grid y / z
     const size_t c = (size_t)M * H * W;
     p->label = 0;
     p->size = (c * sizeof(int32_t) + 15) & ~(size_t)15;
@@ -405,12 +377,8 @@ static bool spk_plan(int32_t M, int32_t H, int32_t W, SpkPlan *p)
 // shape is not taken.
 static int spk_tile_shift(int32_t H, int32_t W)
 {
-    const char *e = getenv("DM_SPECKLE_TILE");
-    int ts = 6;
-    if (e && *e) {
-        const int v = atoi(e);
-        ts = v == 16 ? 4 : v == 32 ? 5 : 6;
-    }
+    int ts = dm_tile_env("DM_SPECKLE_TILE");
+    if (!ts) ts = 6;
     if ((((long long)H + (1 << ts) - 1) >> ts) > 65535 || (((long long)W + (1 << ts) - 1) >> ts) > 65535) ts = 6;
     return ts;
 }
@@ -427,20 +395,20 @@ int dm_filter_speckles(const double *d_in, int32_t M, int32_t H, int32_t W, int3
                        double *d_out, uint8_t *d_removed, uint32_t *d_size, int32_t *d_label, void *d_work,
                        void *stream)
 {
-    if (!d_in || !d_out || !d_work) return sfail(DM_ERR_ARG, "null input / output / workspace pointer");
-    if (M < 1 || H < 1 || W < 1) return sfail(DM_ERR_ARG, "bad speckle shape M=%d H=%d W=%d", M, H, W);
-    if (max_size < 0) return sfail(DM_ERR_ARG, "max_size must be >= 0 (got %d)", max_size);
-    if (!(max_diff >= 0.0)) return sfail(DM_ERR_ARG, "max_diff must be >= 0 (got %g)", max_diff);
+    if (!d_in || !d_out || !d_work) return dm_fail(DM_ERR_ARG, "null input / output / workspace pointer");
+    if (M < 1 || H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad speckle shape M=%d H=%d W=%d", M, H, W);
+    if (max_size < 0) return dm_fail(DM_ERR_ARG, "max_size must be >= 0 (got %d)", max_size);
+    if (!(max_diff >= 0.0)) return dm_fail(DM_ERR_ARG, "max_diff must be >= 0 (got %g)", max_diff);
     SpkPlan p;
     if (!spk_plan(M, H, W, &p))
-        return sfail(DM_ERR_UNSUPPORTED,
+        return dm_fail(DM_ERR_UNSUPPORTED,
                      "speckle filter of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)", M, H, W);
     hipStream_t st = (hipStream_t)stream;
     static bool attr_set = false; // idempotent attributes, benign race
     if (!attr_set) {
-        SHIP_TRY(hipFuncSetAttribute((const void *)k_spk_one, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_spk_one, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)SPK_ONE_LDS));
-        SHIP_TRY(hipFuncSetAttribute((const void *)k_spk_local, hipFuncAttributeMaxDynamicSharedMemorySize,
+        DM_HIP_TRY(hipFuncSetAttribute((const void *)k_spk_local, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)SPK_LOCAL_LDS));
         attr_set = true;
     }
@@ -450,23 +418,23 @@ int dm_filter_speckles(const double *d_in, int32_t M, int32_t H, int32_t W, int3
     if (H <= T && W <= T) {      // the whole map in one tile: one launch, no workspace
         k_spk_one<<<M, SPK_THREADS, tc * (sizeof(double) + sizeof(int) + sizeof(uint32_t)), st>>>(
             d_in, H, W, ts, max_size, max_diff, (unsigned long long *)d_out, d_removed, d_size, d_label);
-        SHIP_TRY(hipGetLastError());
+        DM_HIP_TRY(hipGetLastError());
         return DM_OK;
     }
     int32_t *L = (int32_t *)((char *)d_work + p.label);
     uint32_t *S = (uint32_t *)((char *)d_work + p.size);
     const dim3 grid((W + T - 1) >> ts, (H + T - 1) >> ts, M);
     k_spk_local<<<grid, SPK_THREADS, tc * (sizeof(double) + sizeof(int)), st>>>(d_in, H, W, ts, max_diff, L, S);
-    SHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     k_spk_border<<<grid, 2 * SPK_TMAX, 0, st>>>(d_in, H, W, ts, max_diff, L);
-    SHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     k_spk_count<<<grid, SPK_THREADS, 0, st>>>(H, W, ts, L, S);
-    SHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     const int cells = H * W;
     const dim3 agrid((unsigned)(((long long)cells + SPK_THREADS - 1) / SPK_THREADS), M);
     k_spk_apply<<<agrid, SPK_THREADS, 0, st>>>((const unsigned long long *)d_in, cells, max_size, L, S,
                                                (unsigned long long *)d_out, d_removed, d_size, d_label);
-    SHIP_TRY(hipGetLastError());
+    DM_HIP_TRY(hipGetLastError());
     return DM_OK;
 }
 

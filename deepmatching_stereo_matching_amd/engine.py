@@ -682,6 +682,78 @@ def stitch(match, n, h0, w0, stride, modes, stream=None):
     return dmap, score
 
 
+# ---- argument plumbing of the d_map stages below (fill_holes ... photo_refine) -------------------
+def _int_in(x, lo, hi, msg, got=None):
+    """int(x) of an int (not a bool) in [lo, hi]; else ValueError(msg % (got or x,))."""
+    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
+        raise ValueError(msg % ((x if got is None else got),))
+    return int(x)
+
+
+def _real_in(x, lo, hi, msg, open_lo=False):
+    """float(x) of a real (not a bool) in [lo, hi], or (lo, hi] with ``open_lo``; else ValueError(msg % (x,))."""
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or \
+            not ((lo < float(x) if open_lo else lo <= float(x)) and float(x) <= hi):
+        raise ValueError(msg % (x,))
+    return float(x)
+
+
+def _maps_shape(maps, msg='maps must be a float64 device (cuda) tensor'):
+    """(shape, M, H, W) of a float64 device tensor [H][W] (M = 1) or [M][H][W]; else ValueError."""
+    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
+        raise ValueError(msg)
+    if maps.dim() not in (2, 3):
+        raise ValueError('maps must be [H][W] or [M][H][W]')
+    shape = tuple(maps.shape)
+    return (shape,) + ((1,) + shape if maps.dim() == 2 else shape)
+
+
+def _check_out(out, maps):
+    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
+                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
+        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+
+
+def _src_out(maps, out):
+    """(src, out) of a stage: in place (``out`` is ``maps``' memory) the kernel reads ``out``; else a
+    contiguous ``maps``, and a new ``out`` if none was given."""
+    if out is not None and out.data_ptr() == maps.data_ptr():
+        return out, out
+    if out is None:
+        out = torch.empty(tuple(maps.shape), dtype=torch.float64, device=maps.device)
+    return maps.contiguous(), out
+
+
+def _workspace(nbytes, device, msg):
+    """The stage's workspace of ``nbytes`` (its dm_*_bytes entry); 0 bytes: a shape the stage does
+    not take, NotImplementedError(msg)."""
+    if not nbytes:
+        raise NotImplementedError(msg)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _offset(offset):
+    """``offset``: an int or (oy, ox) -> (oy, ox)."""
+    if isinstance(offset, (tuple, list)):
+        if len(offset) != 2:
+            raise ValueError('offset must be an int or (oy, ox)')
+        oy, ox = offset
+    else:
+        oy = ox = offset
+    msg = 'offset must be an int or (oy, ox) in [-2^30, 2^30] (got %r)'
+    return _int_in(oy, -2 ** 30, 2 ** 30, msg, offset), _int_in(ox, -2 ** 30, 2 ** 30, msg, offset)
+
+
+def _planes_device(d_row, d_col):
+    """The device of the two 2-D float64 device planes of one shape; else ValueError."""
+    for name, d in (('d_row', d_row), ('d_col', d_col)):
+        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.float64 and d.dim() == 2):
+            raise ValueError('%s must be a 2-D float64 device (cuda) tensor' % name)
+    if d_row.shape != d_col.shape or d_row.device != d_col.device:
+        raise ValueError('d_row and d_col must have one shape and device')
+    return d_row.device
+
+
 def fill_iterations(fill):
     """The ``fill=`` keyword of ImageCutSolver / shard.solve_image_sharded as a Jacobi step
     count: an int in [0, 4096] (dm_fill_holes' range)."""
@@ -700,31 +772,17 @@ def fill_holes(maps, iters=16, out=None, return_holes=False, stream=None):
     the result is finite everywhere unless a whole map is a hole (it is then returned as it
     is).  -> the filled tensor: ``out`` if given (``out=maps`` fills in place), else a new one;
     with ``return_holes`` also the uint8 mask of the cells that were holes."""
-    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
-        raise ValueError('maps must be a float64 device (cuda) tensor')
-    if maps.dim() not in (2, 3):
-        raise ValueError('maps must be [H][W] or [M][H][W]')
+    shape, M, H, W = _maps_shape(maps)
     iters = fill_iterations(iters)
-    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
-                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
-        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
-    shape = tuple(maps.shape)
-    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    _check_out(out, maps)
     with _on(stream):
-        if out is not None and out.data_ptr() == maps.data_ptr():
-            src = out
-        else:
-            src = maps.contiguous()
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        src, out = _src_out(maps, out)
         if maps.numel() == 0:      # no cell, no hole
             holes = torch.empty(shape, dtype=torch.uint8, device=maps.device)
             return (out, holes) if return_holes else out
         lib = L.load()
-        nbytes = lib.dm_fill_bytes(M, H, W)
-        if not nbytes:
-            raise NotImplementedError('fill_holes does not take %d maps of %d x %d cells' % (M, H, W))
-        work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+        work = _workspace(lib.dm_fill_bytes(M, H, W), maps.device,
+                          'fill_holes does not take %d maps of %d x %d cells' % (M, H, W))
         holes = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_holes else None
         L.check(lib.dm_fill_holes(L.ptr(src), M, H, W, int(iters), L.ptr(out), L.ptr(holes), L.ptr(work),
                                   L.stream_handle()), 'dm_fill_holes')
@@ -738,12 +796,8 @@ def speckle_params(speckle):
     if isinstance(speckle, (str, bytes)) or not isinstance(speckle, (tuple, list)) or len(speckle) != 2:
         raise ValueError('speckle must be a (max_size, max_diff) pair or None')
     max_size, max_diff = speckle
-    if isinstance(max_size, bool) or not isinstance(max_size, (int, np.integer)) or not 0 <= int(max_size) < 2 ** 31:
-        raise ValueError('speckle max_size must be an int >= 0 (got %r)' % (max_size,))
-    if isinstance(max_diff, bool) or not isinstance(max_diff, (int, float, np.integer, np.floating)) \
-            or not float(max_diff) >= 0.0:
-        raise ValueError('speckle max_diff must be a real >= 0 (got %r)' % (max_diff,))
-    return int(max_size), float(max_diff)
+    return (_int_in(max_size, 0, 2 ** 31 - 1, 'speckle max_size must be an int >= 0 (got %r)'),
+            _real_in(max_diff, 0.0, np.inf, 'speckle max_diff must be a real >= 0 (got %r)'))
 
 
 def filter_speckles(maps, max_size, max_diff, out=None, return_removed=False, return_sizes=False,
@@ -755,32 +809,18 @@ def filter_speckles(maps, max_size, max_diff, out=None, return_removed=False, re
     if given (``out=maps`` filters in place), else a new one; then, as asked for, the uint8
     mask of the cells removed, the size of each cell's segment (0 at holes; an int32 tensor,
     sizes are at most 2^31 - 1) and its int32 label, the smallest linear index of the segment (-1 at holes)."""
-    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
-        raise ValueError('maps must be a float64 device (cuda) tensor')
-    if maps.dim() not in (2, 3):
-        raise ValueError('maps must be [H][W] or [M][H][W]')
+    shape, M, H, W = _maps_shape(maps)
     max_size, max_diff = speckle_params((max_size, max_diff))
-    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
-                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
-        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
-    shape = tuple(maps.shape)
-    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    _check_out(out, maps)
     with _on(stream):
-        if out is not None and out.data_ptr() == maps.data_ptr():
-            src = out
-        else:
-            src = maps.contiguous()
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        src, out = _src_out(maps, out)
         removed = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_removed else None
         sizes = torch.empty(shape, dtype=torch.int32, device=maps.device) if return_sizes else None
         labels = torch.empty(shape, dtype=torch.int32, device=maps.device) if return_labels else None
         if maps.numel():      # (no cell, no segment)
             lib = L.load()
-            nbytes = lib.dm_speckle_bytes(M, H, W)
-            if not nbytes:
-                raise NotImplementedError('filter_speckles does not take %d maps of %d x %d cells' % (M, H, W))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            work = _workspace(lib.dm_speckle_bytes(M, H, W), maps.device,
+                              'filter_speckles does not take %d maps of %d x %d cells' % (M, H, W))
             L.check(lib.dm_filter_speckles(L.ptr(src), M, H, W, max_size, max_diff, L.ptr(out), L.ptr(removed),
                                            L.ptr(sizes), L.ptr(labels), L.ptr(work), L.stream_handle()),
                     'dm_filter_speckles')
@@ -795,12 +835,9 @@ def smooth_params(smooth):
     if isinstance(smooth, (str, bytes)) or not isinstance(smooth, (tuple, list)) or len(smooth) != 3:
         raise ValueError('smooth must be a (radius, sigma_color, sigma_space) triple or None')
     radius, sigma_color, sigma_space = smooth
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 15:
-        raise ValueError('smooth radius must be an int in [1, 15] (got %r)' % (radius,))
-    for name, s in (('sigma_color', sigma_color), ('sigma_space', sigma_space)):
-        if isinstance(s, bool) or not isinstance(s, (int, float, np.integer, np.floating)) or not float(s) > 0.0:
-            raise ValueError('smooth %s must be a real > 0 (got %r)' % (name, s))
-    return int(radius), float(sigma_color), float(sigma_space)
+    return (_int_in(radius, 1, 15, 'smooth radius must be an int in [1, 15] (got %r)'),
+            _real_in(sigma_color, 0.0, np.inf, 'smooth sigma_color must be a real > 0 (got %r)', open_lo=True),
+            _real_in(sigma_space, 0.0, np.inf, 'smooth sigma_space must be a real > 0 (got %r)', open_lo=True))
 
 
 def bilateral_filter(maps, radius, sigma_color, sigma_space, guide=None, iters=1, fill=False, out=None,
@@ -815,14 +852,9 @@ def bilateral_filter(maps, radius, sigma_color, sigma_space, guide=None, iters=1
     guide): a hole is then filled from the usable cells of its window, if any.  -> the smoothed
     tensor: ``out`` if given (``out=maps`` smooths in place), else a new one; with
     ``return_filled`` also the uint8 mask of the holes that came out finite."""
-    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
-        raise ValueError('maps must be a float64 device (cuda) tensor')
-    if maps.dim() not in (2, 3):
-        raise ValueError('maps must be [H][W] or [M][H][W]')
+    shape, M, H, W = _maps_shape(maps)
     radius, sigma_color, sigma_space = smooth_params((radius, sigma_color, sigma_space))
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= 64:
-        raise ValueError('iters must be an int in [1, 64] (got %r)' % (iters,))
-    shape = tuple(maps.shape)
+    iters = _int_in(iters, 1, 64, 'iters must be an int in [1, 64] (got %r)')
     flags = 0
     if guide is not None:
         if not (isinstance(guide, torch.Tensor) and guide.device == maps.device and
@@ -836,24 +868,14 @@ def bilateral_filter(maps, radius, sigma_color, sigma_space, guide=None, iters=1
         if guide is None:
             raise ValueError('fill needs a guide')
         flags |= L.DM_BILAT_FILL
-    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
-                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
-        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
-    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    _check_out(out, maps)
     with _on(stream):
-        if out is not None and out.data_ptr() == maps.data_ptr():
-            src = out
-        else:
-            src = maps.contiguous()
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        src, out = _src_out(maps, out)
         filled = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_filled else None
         if maps.numel():      # (no cell, nothing to smooth)
             lib = L.load()
-            nbytes = lib.dm_bilateral_bytes(M, H, W)
-            if not nbytes:
-                raise NotImplementedError('bilateral_filter does not take %d maps of %d x %d cells' % (M, H, W))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            work = _workspace(lib.dm_bilateral_bytes(M, H, W), maps.device,
+                              'bilateral_filter does not take %d maps of %d x %d cells' % (M, H, W))
             g = guide.contiguous() if guide is not None else None
             gmaps = M if g is not None and g.dim() == 3 else 1
             L.check(lib.dm_bilateral_filter(L.ptr(src), L.ptr(g), gmaps, M, H, W, radius, bilateral_den(sigma_color),
@@ -892,11 +914,8 @@ def median_params(median):
         radius, iters = median[0], (median[1] if len(median) == 2 else 1)
     else:
         radius, iters = median, 1
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
-        raise ValueError('median radius must be an int in [1, 7] (got %r)' % (radius,))
-    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or not 1 <= int(iters) <= 64:
-        raise ValueError('median iters must be an int in [1, 64] (got %r)' % (iters,))
-    return int(radius), int(iters)
+    return (_int_in(radius, 1, 7, 'median radius must be an int in [1, 7] (got %r)'),
+            _int_in(iters, 1, 64, 'median iters must be an int in [1, 64] (got %r)'))
 
 
 def median_filter(maps, radius, weight=None, iters=1, min_count=1, fill=False, out=None, return_changed=False,
@@ -917,15 +936,10 @@ def median_filter(maps, radius, weight=None, iters=1, min_count=1, fill=False, o
         if maps.dtype != np.float64:
             raise ValueError('maps must be float64')
         maps = torch.from_numpy(np.ascontiguousarray(maps)).to(default_device())
-    if not (isinstance(maps, torch.Tensor) and maps.is_cuda and maps.dtype == torch.float64):
-        raise ValueError('maps must be a float64 device (cuda) tensor or a float64 numpy array')
-    if maps.dim() not in (2, 3):
-        raise ValueError('maps must be [H][W] or [M][H][W]')
+    shape, M, H, W = _maps_shape(maps, 'maps must be a float64 device (cuda) tensor or a float64 numpy array')
     radius, iters = median_params((radius, iters))
     K = (2 * radius + 1) ** 2
-    if isinstance(min_count, bool) or not isinstance(min_count, (int, np.integer)) or not 1 <= int(min_count) <= K:
-        raise ValueError('min_count must be an int in [1, %d] (got %r)' % (K, min_count))
-    shape = tuple(maps.shape)
+    min_count = _int_in(min_count, 1, K, 'min_count must be an int in [1, %d] (got %%r)' % K)
     if weight is not None:
         if isinstance(weight, np.ndarray):
             if weight.dtype != np.float64:
@@ -935,24 +949,14 @@ def median_filter(maps, radius, weight=None, iters=1, min_count=1, fill=False, o
             raise ValueError('weight must be a float64 tensor on maps\' device')
         if tuple(weight.shape) not in (shape, shape[-2:]):
             raise ValueError('weight must be [H][W] or of maps\' shape')
-    if out is not None and not (isinstance(out, torch.Tensor) and out.device == maps.device and
-                                out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
-        raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
-    M, H, W = (1,) + shape if maps.dim() == 2 else shape
+    _check_out(out, maps)
     with _on(stream):
-        if out is not None and out.data_ptr() == maps.data_ptr():
-            src = out
-        else:
-            src = maps.contiguous()
-            if out is None:
-                out = torch.empty(shape, dtype=torch.float64, device=maps.device)
+        src, out = _src_out(maps, out)
         changed = torch.empty(shape, dtype=torch.uint8, device=maps.device) if return_changed else None
         if maps.numel():      # (no cell, nothing to filter)
             lib = L.load()
-            nbytes = lib.dm_median_bytes(M, H, W)
-            if not nbytes:
-                raise NotImplementedError('median_filter does not take %d maps of %d x %d cells' % (M, H, W))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=maps.device)
+            work = _workspace(lib.dm_median_bytes(M, H, W), maps.device,
+                              'median_filter does not take %d maps of %d x %d cells' % (M, H, W))
             w = weight.contiguous() if weight is not None else None
             wmaps = M if w is not None and w.dim() == 3 else 1
             L.check(lib.dm_median_filter(L.ptr(src), L.ptr(w), wmaps, M, H, W, radius, int(min_count), iters,
@@ -977,15 +981,10 @@ def photo_params(photo):
         if len(photo) != 2:
             raise ValueError('photo must be a radius, (radius, min_score) or None')
         radius, min_score = photo
-        if isinstance(min_score, bool) or not isinstance(min_score, (int, float, np.integer, np.floating)) or \
-                not -1.0 <= float(min_score) <= 1.0:
-            raise ValueError('photo min_score must be a real in [-1, 1] (got %r)' % (min_score,))
-        min_score = float(min_score)
+        min_score = _real_in(min_score, -1.0, 1.0, 'photo min_score must be a real in [-1, 1] (got %r)')
     else:
         radius, min_score = photo, None
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
-        raise ValueError('photo radius must be an int in [1, 7] (got %r)' % (radius,))
-    return int(radius), min_score
+    return _int_in(radius, 1, 7, 'photo radius must be an int in [1, 7] (got %r)'), min_score
 
 
 def _photo_image(img, device):
@@ -1031,30 +1030,15 @@ def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps
     -> score [H][W]; with ``min_score`` (score, rejected maps); then, when asked for, the warped
     plane (img2 resampled at the centre; NaN outside the image) and the uint8 mask of the
     rejected cells (``return_rejected`` needs ``min_score``) are appended."""
-    for name, d in (('d_row', d_row), ('d_col', d_col)):
-        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.float64 and d.dim() == 2):
-            raise ValueError('%s must be a 2-D float64 device (cuda) tensor' % name)
-    if d_row.shape != d_col.shape or d_row.device != d_col.device:
-        raise ValueError('d_row and d_col must have one shape and device')
-    dev = d_row.device
+    dev = _planes_device(d_row, d_col)
     radius = photo_params(radius)[0]
-    if isinstance(offset, (tuple, list)):
-        if len(offset) != 2:
-            raise ValueError('offset must be an int or (oy, ox)')
-        oy, ox = offset
-    else:
-        oy = ox = offset
-    for o in (oy, ox):
-        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not -2 ** 30 <= int(o) <= 2 ** 30:
-            raise ValueError('offset must be an int or (oy, ox) in [-2^30, 2^30] (got %r)' % (offset,))
+    oy, ox = _offset(offset)
     if min_score is not None:
         min_score = photo_params((radius, min_score))[1]
         if not (isinstance(maps, torch.Tensor) and maps.device == dev and maps.dtype == torch.float64 and
                 maps.dim() in (2, 3) and maps.shape[-2:] == d_row.shape):
             raise ValueError('min_score needs maps: a float64 tensor [H][W] or [M][H][W] on the planes\' device')
-        if out is not None and not (isinstance(out, torch.Tensor) and out.device == dev and
-                                    out.dtype == torch.float64 and out.shape == maps.shape and out.is_contiguous()):
-            raise ValueError('out must be a contiguous float64 tensor of maps\' shape on its device')
+        _check_out(out, maps)
     else:
         if maps is not None or out is not None:
             raise ValueError('maps and out need min_score')
@@ -1080,10 +1064,8 @@ def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps
             if not a.numel():
                 raise ValueError('empty image')
             lib = L.load()
-            nbytes = lib.dm_photo_bytes(M, H, W)
-            if not nbytes:
-                raise NotImplementedError('photo_score does not take %d maps of %d x %d cells' % (M, H, W))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            work = _workspace(lib.dm_photo_bytes(M, H, W), dev,
+                              'photo_score does not take %d maps of %d x %d cells' % (M, H, W))
             L.check(lib.dm_photo_score(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
                                        L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
                                        radius, L.DM_PHOTO_REJECT if min_score is not None else 0,
@@ -1118,14 +1100,9 @@ def refine_params(refine):
         raise ValueError('refine must be (radius, search), (radius, search, min_gain) or None')
     radius, search = refine[0], refine[1]
     min_gain = refine[2] if len(refine) == 3 else 0.0
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 1 <= int(radius) <= 7:
-        raise ValueError('refine radius must be an int in [1, 7] (got %r)' % (radius,))
-    if isinstance(search, bool) or not isinstance(search, (int, np.integer)) or not 1 <= int(search) <= 3:
-        raise ValueError('refine search must be an int in [1, 3] (got %r)' % (search,))
-    if isinstance(min_gain, bool) or not isinstance(min_gain, (int, float, np.integer, np.floating)) or \
-            not 0.0 <= float(min_gain) <= 2.0:
-        raise ValueError('refine min_gain must be a real in [0, 2] (got %r)' % (min_gain,))
-    return int(radius), int(search), float(min_gain)
+    return (_int_in(radius, 1, 7, 'refine radius must be an int in [1, 7] (got %r)'),
+            _int_in(search, 1, 3, 'refine search must be an int in [1, 3] (got %r)'),
+            _real_in(min_gain, 0.0, 2.0, 'refine min_gain must be a real in [0, 2] (got %r)'))
 
 
 def refine_planes(modes):
@@ -1163,22 +1140,9 @@ def photo_refine(img1, img2, d_row, d_col, radius, search, offset=0, min_gain=0.
     contiguous), else new tensors.
     -> (d_row', d_col'); then, when asked for, the float64 score of the position kept (NaN for a
     skipped cell) and the int8 shift [2][H][W] (dy, dx) are appended."""
-    for name, d in (('d_row', d_row), ('d_col', d_col)):
-        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dtype == torch.float64 and d.dim() == 2):
-            raise ValueError('%s must be a 2-D float64 device (cuda) tensor' % name)
-    if d_row.shape != d_col.shape or d_row.device != d_col.device:
-        raise ValueError('d_row and d_col must have one shape and device')
-    dev = d_row.device
+    dev = _planes_device(d_row, d_col)
     radius, search, min_gain = refine_params((radius, search, min_gain))
-    if isinstance(offset, (tuple, list)):
-        if len(offset) != 2:
-            raise ValueError('offset must be an int or (oy, ox)')
-        oy, ox = offset
-    else:
-        oy = ox = offset
-    for o in (oy, ox):
-        if isinstance(o, bool) or not isinstance(o, (int, np.integer)) or not -2 ** 30 <= int(o) <= 2 ** 30:
-            raise ValueError('offset must be an int or (oy, ox) in [-2^30, 2^30] (got %r)' % (offset,))
+    oy, ox = _offset(offset)
     if mask is not None:
         if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
                 mask.shape == d_row.shape):
@@ -1201,11 +1165,9 @@ def photo_refine(img1, img2, d_row, d_col, radius, search, offset=0, min_gain=0.
             if not a.numel():
                 raise ValueError('empty image')
             lib = L.load()
-            nbytes = lib.dm_photo_refine_bytes(a.shape[0], a.shape[1], H, W, radius, search)
-            if not nbytes:
-                raise NotImplementedError('photo_refine does not take %d x %d cells on a %d x %d image' %
-                                          (H, W, a.shape[0], a.shape[1]))
-            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            work = _workspace(lib.dm_photo_refine_bytes(a.shape[0], a.shape[1], H, W, radius, search), dev,
+                              'photo_refine does not take %d x %d cells on a %d x %d image' %
+                              (H, W, a.shape[0], a.shape[1]))
             m = None if mask is None else mask.to(torch.uint8).contiguous()
             # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
             L.check(lib.dm_photo_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],

@@ -12,7 +12,7 @@ import torch
 from PIL import Image
 
 from deepmatching_stereo_matching_amd import _lib as L
-from deepmatching_stereo_matching_amd import engine
+from deepmatching_stereo_matching_amd import chain, engine
 
 
 class ImageCutSolver():
@@ -73,9 +73,6 @@ class ImageCutSolver():
         # forward-backward consistency tolerance in pixels (None: the reference's behaviour)
         self.consistency = consistency
         self.consistency_map = None
-        # Jacobi iterations of the hole fill of d_map (engine.fill_holes); None: d_map keeps its NaN
-        self.fill = engine.fill_iterations(fill) if fill is not None else None
-        self.hole_map = None
         # rule that merges the overlapping tiles of a pixel (engine.stitch_merge); None: the last tile wins
         if merge is not None:
             engine.merge_rule(merge)
@@ -83,47 +80,31 @@ class ImageCutSolver():
         self.merge_min_count = merge_min_count
         self.coverage_map = None
         self.spread_map = None
-        # (max_size, max_diff) of the speckle filter of d_map (engine.filter_speckles), run after the
-        # stitch and before the fill; None: no segment is removed
-        self.speckle = engine.speckle_params(speckle) if speckle is not None else None
-        self.speckle_map = None
-        # (radius, sigma_color, sigma_space) of the bilateral smoothing of d_map (engine.bilateral_filter),
-        # run last: after the stitch, the speckle filter and the fill; None: d_map is not smoothed.
-        # smooth_guide: 'image' (img1 under the map's cells, uint8) or 'self' (the map guides itself)
-        self.smooth = engine.smooth_params(smooth) if smooth is not None else None
-        if smooth_guide not in ('image', 'self'):
-            raise ValueError("smooth_guide must be 'image' or 'self'")
-        self.smooth_guide = smooth_guide
-        # radius, (radius,) or (radius, iters) of the median filter of d_map (engine.median_filter), run
-        # immediately after the stitch: impulses go first, then blobs (speckle), holes (fill), smoothing;
-        # None: no median.  median_weight: None (unweighted) or 'correlation' (weighted by out_map)
-        self.median = engine.median_params(median) if median is not None else None
-        if median_weight not in (None, 'correlation'):
-            raise ValueError("median_weight must be None or 'correlation'")
-        self.median_weight = median_weight
-        # radius or (radius, min_score) of the photo-consistency score (engine.photo_score): img2 is
-        # resampled where d_map claims the match and correlated with img1 around the cell.  photo_map is
-        # the score of the final d_map; with min_score the cells scoring below it are also rejected
-        # (NaN in every mode) after the median and before the speckle filter, and photo_reject_map marks
-        # them.  Needs both 'elevation' and 'elevation2' in degree_map_mode.  None: nothing is scored
-        self.photo = engine.photo_params(photo) if photo is not None else None
-        if self.photo is not None:
-            engine.photo_planes(degree_map_mode)
-        self.photo_map = None
-        self.photo_reject_map = None
-        # (radius, search) or (radius, search, min_gain) of the local re-matching (engine.photo_refine), run
-        # after the fill and before the smoothing: a cell scores the (2 search + 1)^2 integer neighbours of
-        # the position it claims and moves to the best one.  refine_where: 'filled' (only the cells the fill
-        # produced; needs fill=) or 'all'.  Needs 'elevation' and 'elevation2' and no 'distance' in
-        # degree_map_mode.  refine_score_map is the score of the position kept (NaN: not refined),
-        # refine_shift_map the int8 shift [2][H][W] (dy, dx).  None: nothing is refined
-        self.refine = engine.refine_params(refine) if refine is not None else None
-        self.refine_where = refine_where
-        if self.refine is not None:
-            engine.refine_planes(degree_map_mode)
-            engine.refine_where(refine_where, self.fill)
-        self.refine_score_map = None
-        self.refine_shift_map = None
+        # The post-processing of the stitched d_map (chain.py has the stages and their order); every
+        # keyword is kept as parsed, None: the stage is off.
+        #   fill: Jacobi iterations of the hole fill; hole_map marks the cells that were filled
+        #   speckle: (max_size, max_diff) of the speckle filter; speckle_map marks the cells removed
+        #   smooth: (radius, sigma_color, sigma_space) of the bilateral smoothing; smooth_guide: 'image'
+        #       (img1 under the map's cells, uint8) or 'self' (the map guides itself)
+        #   median: radius, (radius,) or (radius, iters) of the median filter; median_weight: None
+        #       (unweighted) or 'correlation' (weighted by out_map)
+        #   photo: radius or (radius, min_score) of the photo-consistency score: img2 is resampled where
+        #       d_map claims the match and correlated with img1 around the cell.  photo_map is the score of
+        #       the final d_map; with min_score the cells scoring below it are also rejected (NaN in every
+        #       mode) and photo_reject_map marks them.  Needs 'elevation' and 'elevation2' in degree_map_mode
+        #   refine: (radius, search) or (radius, search, min_gain) of the local re-matching: a cell scores the
+        #       (2 search + 1)^2 integer neighbours of the position it claims and moves to the best one.
+        #       refine_where: 'filled' (only the cells the fill produced; needs fill=) or 'all'.  Needs
+        #       'elevation' and 'elevation2' and no 'distance' in degree_map_mode.  refine_score_map is the
+        #       score of the position kept (NaN: not refined), refine_shift_map the int8 shift [2][H][W]
+        self.chain = chain.Chain(degree_map_mode, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide,
+                                 median=median, median_weight=median_weight, photo=photo, refine=refine,
+                                 refine_where=refine_where)
+        for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
+                     'refine_where'):
+            setattr(self, name, getattr(self.chain, name))
+        self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
+        self.refine_score_map = self.refine_shift_map = None
 
         self.log_flg = True
 
@@ -185,29 +166,12 @@ class ImageCutSolver():
         others get None).  Every rank must then solve the same pair (shard.broadcast_pair
         sends it from rank 0).  With self.consistency set both branches solve the pair in both
         directions and return a third tensor, the stitched round-trip error (engine.stitch_fb).
-        With self.fill set d_map comes back filled (engine.fill_holes) and the uint8 mask of the
-        cells that were filled is the last tensor.  With self.merge set the stitch is
-        engine.stitch_merge (both directions when self.consistency is set) and the spread and the
-        uint8 count of valid candidates follow out_map / the error, before the hole mask.  With
-        self.speckle set d_map loses its small segments (engine.filter_speckles) after the stitch
-        and before the fill, and the uint8 mask of the cells removed comes immediately before the
-        hole mask: (d_map, out_map[, err][, spread, count][, speckles][, holes]).  With self.smooth
-        set d_map is smoothed last (engine.bilateral_filter, all modes in one call; holes stay
-        holes, self.fill is what fills); no tensor is added.  With self.median set d_map is median
-        filtered first, immediately after the stitch and before the speckle filter, the fill and the
-        smoothing (engine.median_filter, all modes in one call, in place, weighted by out_map when
-        self.median_weight is 'correlation'; holes stay holes); no tensor is added.  With self.photo
-        set the final d_map is scored last (engine.photo_score against self.img1 / self.img2, map cell
-        (y, x) at pixel (y + e, x + e), e = exclusive_pix) and the float64 score [H][W] is appended
-        after every other tensor; with a min_score the cells that score below it are first rejected
-        in every mode, after the median and before the speckle filter, and the uint8 mask [H][W] of
-        those cells comes immediately before the score.  The chain is stitch -> median -> photo
-        reject -> speckle -> fill -> smooth -> photo score, the tuple (d_map, out_map[, err]
-        [, spread, count][, speckles][, holes][[, rejected], score]).  With self.refine set the cells
-        are matched again locally (engine.photo_refine) after the fill and before the smoothing --
-        only the filled ones with refine_where='filled' -- and the float64 score and the int8 shift
-        [2][H][W] come immediately before the photo tensors: (d_map, out_map[, err][, spread, count]
-        [, speckles][, holes][, refine score, refine shift][[, rejected], score])."""
+        With self.merge set the stitch is engine.stitch_merge (both directions when
+        self.consistency is set) and the spread and the uint8 count of valid candidates follow
+        out_map / the error.  The stitched d_map then runs through self.chain (chain.py: the stages
+        that self.fill, self.speckle, self.smooth, self.median, self.photo and self.refine switch on,
+        against self.img1 / self.img2 with e = exclusive_pix), which appends the tensors of its
+        stages: the tuple is the one chain.Chain.layout names."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -245,66 +209,28 @@ class ImageCutSolver():
         else:
             match = engine.solve_tiles(*args)
             maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
-        if self.median is not None:
-            d = engine.median_filter(maps[0], self.median[0], weight=engine.median_weight(self.median_weight, maps),
-                                     iters=self.median[1], out=maps[0])
-            maps = (d,) + tuple(maps[1:])
-        rejected = None
-        if self.photo is not None and self.photo[1] is not None:
-            d, rejected = engine.photo_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.photo,
-                                             self.exclusive_pix, True)
-            maps = (d,) + tuple(maps[1:])
-        if self.speckle is not None:
-            d, removed = engine.filter_speckles(maps[0], *self.speckle, out=maps[0], return_removed=True)
-            maps = (d,) + tuple(maps[1:]) + (removed,)
-        if self.fill is not None:
-            d, holes = engine.fill_holes(maps[0], self.fill, out=maps[0], return_holes=True)
-            maps = (d,) + tuple(maps[1:]) + (holes,)
-        if self.refine is not None:
-            d, rscore, rshift = engine.refine_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.refine,
-                                                    self.exclusive_pix,
-                                                    maps[-1] if self.refine_where == 'filled' else None)
-            maps = (d,) + tuple(maps[1:]) + (rscore, rshift)
-        if self.smooth is not None:
-            guide = engine.smooth_guide(self.img1, self.exclusive_pix, maps[0]) if self.smooth_guide == 'image' else None
-            d = engine.bilateral_filter(maps[0], *self.smooth, guide=guide, out=maps[0])
-            maps = (d,) + tuple(maps[1:])
-        if self.photo is not None:
-            score = engine.photo_stage(self.img1, self.img2, maps[0], self.degree_map_mode, self.photo,
-                                       self.exclusive_pix, False)
-            maps = tuple(maps) + ((rejected,) if rejected is not None else ()) + (score,)
-        return maps
+        return self.chain.run(maps, self.img1, self.img2, self.exclusive_pix, self.consistency, self.merge)
+
+    # attribute: (entry of chain.Chain.layout, a uint8 mask that is kept as bool)
+    _MAPS = {'d_map': ('d_map', False), 'out_map': ('out_map', False),
+             'consistency_map': ('err', False),        # round-trip error; d_map is NaN where it exceeds the tolerance
+             'spread_map': ('spread', False),          # max - min of the valid candidates of a pixel, per mode
+             'coverage_map': ('count', False),         # their number
+             'speckle_map': ('speckles', True),        # the cells the speckle filter removed (before any fill)
+             'hole_map': ('holes', True),              # d_map is dense; the cells that were filled
+             'refine_score_map': ('refine_score', False), 'refine_shift_map': ('refine_shift', False),
+             'photo_reject_map': ('rejected', True),   # the cells scoring below min_score (before any fill)
+             'photo_map': ('score', False)}
 
     def _execute_matching(self):
         """
         小画像ごとにマッチングを行い結果を結合
         """
-        maps = self._execute_matching_device()
-        if self.photo is not None:         # the last tensors: taken off first, the indices below stay as they were
-            self.photo_map = maps[-1].cpu().numpy() if maps[-1] is not None else None
-            maps = maps[:-1]
-            if self.photo[1] is not None:  # the cells rejected for scoring below min_score (before any fill)
-                self.photo_reject_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
-                maps = maps[:-1]
-        if self.refine is not None:        # immediately before the photo tensors: taken off next
-            self.refine_shift_map = maps[-1].cpu().numpy() if maps[-1] is not None else None
-            self.refine_score_map = maps[-2].cpu().numpy() if maps[-2] is not None else None
-            maps = maps[:-2]
-        d_map, out_map = maps[0], maps[1]
-        # (None on the ranks other than 0 of a sharded solve with tile_sharding(result='root'))
-        self.d_map = d_map.cpu().numpy() if d_map is not None else None
-        self.out_map = out_map.cpu().numpy() if out_map is not None else None
-        if self.consistency is not None:   # [H][W] round-trip error; d_map is NaN where it exceeds the tolerance
-            self.consistency_map = maps[2].cpu().numpy() if maps[2] is not None else None
-        if self.merge is not None:         # valid candidates per pixel and their max - min, per mode
-            k = 3 if self.consistency is not None else 2
-            self.spread_map = maps[k].cpu().numpy() if maps[k] is not None else None
-            self.coverage_map = maps[k + 1].cpu().numpy() if maps[k + 1] is not None else None
-        if self.speckle is not None:       # the cells the speckle filter removed (before any fill)
-            k = -2 if self.fill is not None else -1
-            self.speckle_map = maps[k].cpu().numpy().astype(bool) if maps[k] is not None else None
-        if self.fill is not None:          # d_map is dense; hole_map marks the cells that were filled
-            self.hole_map = maps[-1].cpu().numpy().astype(bool) if maps[-1] is not None else None
+        maps = dict(zip(self.chain.names(self.consistency, self.merge), self._execute_matching_device()))
+        for attr, (name, mask) in self._MAPS.items():
+            t = maps.get(name)      # absent: the stage is off; None: off rank 0 with tile_sharding(result='root')
+            a = t.cpu().numpy() if t is not None else None
+            setattr(self, attr, a.astype(bool) if mask and a is not None else a)
 
     def __call__(self):
         self._cut_and_pool()

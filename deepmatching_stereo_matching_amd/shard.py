@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import engine
+from . import chain, engine
 
 # Tile sharding of the mirror ImageCutSolver is OPT-IN: a process group alone does not turn it
 # on (ranks that each solve their own pairs, solve_pairs_sharded, must not enter one
@@ -434,8 +434,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     after the median and before the speckle filter (``photoer(img1, img2, d_row, d_col, radius, e,
     min_score, d_map) -> (score, d_map, uint8 mask)``), and the uint8 mask [H][W] comes immediately
     before the score: (d_map, out_map[, err][, spread, count][, speckles][, holes][[, rejected],
-    score]).  None: nothing changes.  The chain is stitch -> median -> photo reject -> speckle ->
-    fill -> smooth -> photo score.
+    score]).  None: nothing changes.
     ``refine``: (radius, search) or (radius, search, min_gain), with both 'elevation' and 'elevation2'
     and no 'distance' in ``modes`` (else ValueError); rank 0 then matches the cells again locally after
     the fill and before the smoothing (engine.photo_refine with the offset e, or ``refiner(img1, img2,
@@ -443,33 +442,18 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     [2][H][W])``).  ``refine_where``: 'filled' -- only the cells the fill produced in either plane;
     needs ``fill`` -- or 'all'.  The float64 score [H][W] and the shift come immediately before the
     photo tensors: (d_map, out_map[, err][, spread, count][, speckles][, holes][, refine score, refine
-    shift][[, rejected], score]).  None: nothing changes.  The chain is stitch -> median -> photo
-    reject -> speckle -> fill -> refine -> smooth -> photo score."""
+    shift][[, rejected], score]).  None: nothing changes.
+    The stages after the stitch, their order and the layout of the tuple are chain.py's (its module
+    docstring states the order once); a hook replaces the device stage of its name there."""
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
-    pho = engine.photo_params(photo) if photo is not None else None
-    if pho is not None:
-        pho_row, pho_col = engine.photo_planes(modes)
-    pho_img1, pho_img2 = img1, img2      # (consistency stacks the pair below)
-    ref = engine.refine_params(refine) if refine is not None else None
-    if ref is not None:
-        ref_row, ref_col = engine.refine_planes(modes)
-        engine.refine_where(refine_where, fill)
-    med = engine.median_params(median) if median is not None else None
-    if median_weight not in (None, 'correlation'):
-        raise ValueError("median_weight must be None or 'correlation'")
-    iters = engine.fill_iterations(fill) if fill is not None else None
-    spk = engine.speckle_params(speckle) if speckle is not None else None
-    smo = engine.smooth_params(smooth) if smooth is not None else None
-    if smooth_guide not in ('image', 'self'):
-        raise ValueError("smooth_guide must be 'image' or 'self'")
-    guide_img = img1      # (consistency stacks the pair below)
+    post = chain.Chain(modes, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide, median=median,
+                       median_weight=median_weight, photo=photo, refine=refine, refine_where=refine_where)
+    pair = img1, img2      # what the stages read (consistency stacks the pair below)
     if merge is not None:
         engine.merge_rule(merge)
     n, origins = grid if grid is not None else engine.cut_grid(np.shape(img1), image_size, stride, window_size)
-    nmaps = 2
     if consistency is not None:
-        nmaps = 3
         T = len(np.asarray(origins).reshape(-1, 2))
         origins = engine.bidir_origins(origins, np.shape(img1)[0])
         img1, img2 = engine.stack_pair(img1, img2)
@@ -477,109 +461,31 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                       chunks=chunks, dst=0, solver=solver)
     match = band.solve(sub_pix=sub_pix, filtering=filtering, filter_window_size=filter_window_size,
                        filtering_num=filtering_num, filtering_mode=filtering_mode)
-    if merge is not None:
-        nmaps += 2
     if match is None:
         maps = None
-    elif merge is not None:
-        fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
-        maps = (merger or engine.stitch_merge)(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes),
-                                               consistency, merge, merge_min_count)
-        maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
-    elif consistency is not None:
-        stitch = stitcher or engine.stitch_fb
-        maps = stitch(match[:T], match[T:], n, image_size[0], image_size[1], stride, list(modes), consistency)
     else:
-        stitch = stitcher or engine.stitch
-        maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
-    if med is not None and maps is not None:
-        weight = engine.median_weight(median_weight, maps)
-        if medianer is not None:
-            d = medianer(maps[0], weight, *med)
+        if merge is not None:
+            fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
+            maps = (merger or engine.stitch_merge)(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes),
+                                                   consistency, merge, merge_min_count)
+            maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
+        elif consistency is not None:
+            stitch = stitcher or engine.stitch_fb
+            maps = stitch(match[:T], match[T:], n, image_size[0], image_size[1], stride, list(modes), consistency)
         else:
-            d = engine.median_filter(maps[0], med[0], weight=weight, iters=med[1], out=maps[0])
-        maps = (d,) + tuple(maps[1:])
-    pho_e = (window_size - 1) // 2
-    rejected = None
-    if pho is not None and pho[1] is not None and maps is not None:
-        if photoer is not None:
-            _, d, rejected = photoer(pho_img1, pho_img2, maps[0][pho_row], maps[0][pho_col], pho[0], pho_e, pho[1],
-                                     maps[0])
-        else:
-            d, rejected = engine.photo_stage(pho_img1, pho_img2, maps[0], modes, pho, pho_e, True)
-        maps = (d,) + tuple(maps[1:])
-    if spk is not None:
-        nmaps += 1
-        if maps is not None:
-            if speckler is not None:
-                d, removed = speckler(maps[0], spk[0], spk[1])
-            else:
-                d, removed = engine.filter_speckles(maps[0], spk[0], spk[1], out=maps[0], return_removed=True)
-            maps = (d,) + tuple(maps[1:]) + (removed,)
-    if iters is not None:
-        nmaps += 1
-        if maps is not None:
-            if filler is not None:
-                d, holes = filler(maps[0], iters)
-            else:
-                d, holes = engine.fill_holes(maps[0], iters, out=maps[0], return_holes=True)
-            maps = (d,) + tuple(maps[1:]) + (holes,)
-    if ref is not None:
-        nmaps += 2
-        if maps is not None:
-            if refiner is not None:
-                holes = maps[-1] if refine_where == 'filled' else None
-                mask = None if holes is None else (np.asarray(holes[ref_row]) | np.asarray(holes[ref_col]))
-                d_row, d_col, rscore, rshift = refiner(pho_img1, pho_img2, maps[0][ref_row], maps[0][ref_col], ref[0],
-                                                       ref[1], pho_e, ref[2], mask)
-                d = maps[0]
-                d[ref_row], d[ref_col] = d_row, d_col
-            else:
-                d, rscore, rshift = engine.refine_stage(pho_img1, pho_img2, maps[0], modes, ref, pho_e,
-                                                        maps[-1] if refine_where == 'filled' else None)
-            maps = (d,) + tuple(maps[1:]) + (rscore, rshift)
-    if smo is not None and maps is not None:
-        e = (window_size - 1) // 2
-        if smoother is not None:
-            Hm, Wm = np.shape(maps[0])[-2:]
-            guide = np.asarray(guide_img)[e:e + Hm, e:e + Wm] if smooth_guide == 'image' else None
-            d = smoother(maps[0], guide, *smo)
-        else:
-            guide = engine.smooth_guide(guide_img, e, maps[0]) if smooth_guide == 'image' else None
-            d = engine.bilateral_filter(maps[0], *smo, guide=guide, out=maps[0])
-        maps = (d,) + tuple(maps[1:])
-    if pho is not None:
-        nmaps += 1 if pho[1] is None else 2
-        if maps is not None:
-            if photoer is not None:
-                score = photoer(pho_img1, pho_img2, maps[0][pho_row], maps[0][pho_col], pho[0], pho_e, None, None)
-            else:
-                score = engine.photo_stage(pho_img1, pho_img2, maps[0], modes, pho, pho_e, False)
-            maps = tuple(maps) + ((rejected,) if pho[1] is not None else ()) + (score,)
+            stitch = stitcher or engine.stitch
+            maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
+        maps = post.run(maps, pair[0], pair[1], (window_size - 1) // 2, consistency, merge, filler=filler,
+                        speckler=speckler, smoother=smoother, medianer=medianer, photoer=photoer, refiner=refiner)
     if not _group() or world()[1] == 1:
         return maps
-    if result == 'root':
-        return maps if maps is not None else (None,) * nmaps
     H = stride[0] * (n[0] - 1) + image_size[0]
     W = stride[1] * (n[1] - 1) + image_size[1]
-    dev = band.device
+    layout = post.layout(H, W, consistency, merge)
+    if result == 'root':
+        return maps if maps is not None else (None,) * len(layout)
     if maps is None:
-        out = [torch.empty((len(modes), H, W), dtype=torch.float64, device=dev)]
-        out += [torch.empty((H, W), dtype=torch.float64, device=dev) for _ in range(2 if consistency is not None else 1)]
-        if merge is not None:
-            out.append(torch.empty((len(modes), H, W), dtype=torch.float64, device=dev))
-            out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
-        if spk is not None:
-            out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
-        if iters is not None:
-            out.append(torch.empty((len(modes), H, W), dtype=torch.uint8, device=dev))
-        if ref is not None:
-            out.append(torch.empty((H, W), dtype=torch.float64, device=dev))
-            out.append(torch.empty((2, H, W), dtype=torch.int8, device=dev))
-        if pho is not None:
-            if pho[1] is not None:
-                out.append(torch.empty((H, W), dtype=torch.uint8, device=dev))
-            out.append(torch.empty((H, W), dtype=torch.float64, device=dev))
+        out = [torch.empty(shape, dtype=dtype, device=band.device) for _, shape, dtype in layout]
     else:
         out = [torch.as_tensor(m) for m in maps]
     for t in out:

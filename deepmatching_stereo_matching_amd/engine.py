@@ -1189,3 +1189,309 @@ def refine_stage(img1, img2, d_map, modes, refine, offset, holes=None):
                                               min_gain=refine[2], mask=mask, out=(d_map[ir], d_map[ic]),
                                               return_score=True, return_shift=True)
     return d_map, score, shift
+
+
+# ---- disparity priors (csrc/dm_prior.hip; include/dmstereo.h has the definitions) ----------------
+def downsample2(img, device=None, stream=None):
+    """The half-resolution image (dm_downsample2): a 2-D uint8 image, a numpy array or a tensor
+    (a view with a row stride is read where it is), -> the uint8 device tensor [H // 2][W // 2] of
+    (a + b + c + d + 2) >> 2 over each 2 x 2 block; an odd last row or column is dropped."""
+    if device is None:
+        device = img.device if isinstance(img, torch.Tensor) and img.is_cuda else default_device()
+    with _on(stream):
+        a = _photo_image(img, device)
+        H, W = a.shape
+        if H < 2 or W < 2:
+            raise ValueError('an image of %d x %d has no 2 x 2 block' % (H, W))
+        out = torch.empty((H // 2, W // 2), dtype=torch.uint8, device=device)
+        L.check(L.load().dm_downsample2(L.ptr(a), a.stride(0), H, W, L.ptr(out), out.stride(0), L.stream_handle()),
+                'dm_downsample2')
+    return out
+
+
+def _tile_shape(h0, w0):
+    msg = 'tile sides must be ints in [1, 65536] (got %r)'
+    return _int_in(h0, 1, 65536, msg), _int_in(w0, 1, 65536, msg)
+
+
+def _origins_host(origins):
+    """Tile origins as a host int64 array [T][2], T >= 1, none negative; else ValueError."""
+    org = np.asarray(origins)
+    if org.dtype.kind not in 'iu' or org.size == 0 or org.size % 2:
+        raise ValueError('origins must be a non-empty int array [T][2]')
+    org = org.astype(np.int64).reshape(-1, 2)
+    if org.min() < 0 or org.max() > 2 ** 30:
+        raise ValueError('origins must lie in [0, 2^30]')
+    return org
+
+
+def _prior_device(prior, T, device):
+    """A prior as a contiguous int32 device tensor [T][2]: an int array or tensor [T][2] (host or
+    device; a device tensor is used where it is, without a look at its values)."""
+    if isinstance(prior, torch.Tensor):
+        if prior.dtype not in (torch.int32, torch.int64) or tuple(prior.shape) != (T, 2):
+            raise ValueError('prior must be an int tensor [%d][2]' % T)
+        return prior.to(device=device, dtype=torch.int32).contiguous()
+    q = np.asarray(prior)
+    if q.dtype.kind not in 'iu' or q.shape != (T, 2):
+        raise ValueError('prior must be an int array [%d][2]' % T)
+    if q.size and np.abs(q.astype(np.int64)).max() > 2 ** 30:
+        raise ValueError('prior must lie in [-2^30, 2^30]')
+    return torch.from_numpy(np.ascontiguousarray(q.astype(np.int32))).to(device)
+
+
+def origins_device(origins, device):
+    """Tile origins as a contiguous int32 device tensor [T][2]: a host int array (checked and
+    uploaded) or such a tensor already on ``device`` (taken as it is: a caller that uploads the
+    origins of several solves ahead keeps the copies out of the way of the kernels)."""
+    if isinstance(origins, torch.Tensor) and origins.is_cuda:
+        if origins.dtype != torch.int32 or origins.dim() != 2 or origins.shape[1] != 2 or not len(origins) or \
+                origins.device != device or not origins.is_contiguous():
+            raise ValueError('device origins must be a contiguous int32 tensor [T][2] on the planes\' device')
+        return origins
+    return torch.from_numpy(_origins_host(origins).astype(np.int32)).to(device)
+
+
+def tile_prior(d_row, d_col, origins, h0, w0, e, scale=2, stream=None):
+    """One integer prior per tile from a map of the pair (dm_tile_prior).  ``d_row``, ``d_col``:
+    float64 device tensors [Hc][Wc], the 'elevation2' and 'elevation' planes of a map whose cell
+    (y, x) sits at pixel (y + e, x + e) of an image ``scale`` (1 or 2) times smaller than the one
+    the tiles (``origins`` [T][2], host or device (origins_device), h0 x w0 cells) are cut from.  A
+    tile's footprint in the map is
+    rows (o_y + e) // scale - e .. (o_y + e + h0 - 1) // scale - e, each end clamped into the map,
+    columns alike; over its cells where both planes are finite, the prior is rint(scale * lower
+    median) per plane.  A tile without such a cell takes the lower median of the other tiles'
+    priors (0 if there is none).  -> (q, valid): int32 [T][2] (row, column) and uint8 [T], 1 for
+    the tiles that measured their own prior; both stay on the device, nothing synchronises."""
+    dev = _planes_device(d_row, d_col)
+    h0, w0 = _tile_shape(h0, w0)
+    e = _int_in(e, 0, 65536, 'e must be an int in [0, 65536] (got %r)')
+    if isinstance(scale, bool) or scale not in (1, 2):
+        raise ValueError('scale must be 1 or 2 (got %r)' % (scale,))
+    if d_row.numel() == 0:
+        raise ValueError('empty map')
+    with _on(stream):
+        o = origins_device(origins, dev)
+        T = len(o)
+        q = torch.empty((T, 2), dtype=torch.int32, device=dev)
+        valid = torch.empty((T,), dtype=torch.uint8, device=dev)
+        L.check(L.load().dm_tile_prior(L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), d_row.shape[0],
+                                       d_row.shape[1], L.ptr(o), T, h0, w0, e, int(scale), L.ptr(q), L.ptr(valid),
+                                       L.stream_handle()), 'dm_tile_prior')
+    return q, valid
+
+
+def pack_grid(T, h0, w0, ws):
+    """Where pack_tiles puts its T crops (dm_pack_plan): (origins, Hp, Wp), the host int64 array
+    [T][2] of the crops' top-left corners in the packed images and the packed images' shape."""
+    gx, Hp, Wp = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    L.check(L.load().dm_pack_plan(int(T), int(h0), int(w0), int(ws), ctypes.byref(gx), ctypes.byref(Hp),
+                                  ctypes.byref(Wp)), 'dm_pack_plan')
+    t = np.arange(int(T), dtype=np.int64)
+    org = np.stack([(t // gx.value) * (int(h0) + int(ws) - 1), (t % gx.value) * (int(w0) + int(ws) - 1)], axis=1)
+    return org, Hp.value, Wp.value
+
+
+def pack_tiles(img1, img2, origins, prior, h0, w0, ws, device=None, stream=None):
+    """The crop pairs of T tiles with a disparity prior, side by side in a fresh image pair
+    (dm_pack_tiles).  Crop t of img1 is cut at origins[t], crop t of img2 at origins[t] - prior[t]
+    clamped per axis into the image, so every packed crop pixel is a real pixel.  ``prior``: int
+    [T][2] (row, column), host or device, in the units and sign of d_map ('elevation2',
+    'elevation').  -> (pack1, pack2, pack_origins, q_eff): the packed uint8 images (one shape,
+    contiguous; TileBatch takes them with pack_grid's origins), the device int32 [T][2] places of
+    the crops (pack_grid's origins) and the device int32 [T][2] effective priors, origins[t] minus
+    the clamped img2 origin.  Nothing synchronises."""
+    device = device or default_device()
+    h0, w0 = _tile_shape(h0, w0)
+    ws = _int_in(ws, 1, 65536, 'window_size must be an int >= 1 (got %r)')
+    org = _origins_host(origins)
+    T = len(org)
+    with _on(stream):
+        a, b = _photo_image(img1, device), _photo_image(img2, device)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        H, W = a.shape
+        # the kernel trusts these bounds as the solver's do (TileBatch): check them here, on the host
+        if (org[:, 0] + h0 + ws - 1).max() > H or (org[:, 1] + w0 + ws - 1).max() > W:
+            raise ValueError('tile crop outside the image')
+        q = _prior_device(prior, T, device)
+        _, Hp, Wp = pack_grid(T, h0, w0, ws)
+        o = torch.from_numpy(org.astype(np.int32)).to(device)
+        p1 = torch.empty((Hp, Wp), dtype=torch.uint8, device=device)
+        p2 = torch.empty((Hp, Wp), dtype=torch.uint8, device=device)
+        porg = torch.empty((T, 2), dtype=torch.int32, device=device)
+        q_eff = torch.empty((T, 2), dtype=torch.int32, device=device)
+        L.check(L.load().dm_pack_tiles(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), H, W, L.ptr(o), L.ptr(q), T,
+                                       h0, w0, ws, L.ptr(p1), L.ptr(p2), L.ptr(porg), L.ptr(q_eff),
+                                       L.stream_handle()), 'dm_pack_tiles')
+    return p1, p2, porg, q_eff
+
+
+def shift_matches(match, q_eff, stream=None):
+    """In place on the matches of a packed solve, a contiguous float64 device tensor
+    [T][3][h0][w0] (dm_shift_matches): rows 0 and 1 of tile t minus q_eff[t] (int32 device
+    [T][2]), which expresses them in the frame of img1's tile; NaN stays NaN, the score row is
+    untouched.  cal_map, stitch and stitch_merge then give global disparities.  -> match."""
+    if not (isinstance(match, torch.Tensor) and match.is_cuda and match.dtype == torch.float64 and
+            match.dim() == 4 and match.shape[1] == 3 and match.is_contiguous() and match.numel()):
+        raise ValueError('match must be a contiguous float64 device tensor [T][3][h0][w0]')
+    T, _, h0, w0 = match.shape
+    if not (isinstance(q_eff, torch.Tensor) and q_eff.device == match.device and q_eff.dtype == torch.int32 and
+            tuple(q_eff.shape) == (T, 2) and q_eff.is_contiguous()):
+        raise ValueError('q_eff must be a contiguous int32 tensor [%d][2] on match\'s device' % T)
+    with _on(stream):
+        L.check(L.load().dm_shift_matches(L.ptr(match), L.ptr(q_eff), T, h0, w0, L.stream_handle()),
+                'dm_shift_matches')
+    return match
+
+
+def consistency_tol(tol):
+    """A forward-backward tolerance in pixels: a real >= 0."""
+    return _real_in(tol, 0.0, np.inf, 'the consistency tolerance must be a real >= 0 (got %r)')
+
+
+def solve_tiles_prior(img1, img2, origins, prior, h0, w0, ws, method, sub_pix=True, filtering=False,
+                      filter_window_size=3, filtering_num=3, filtering_mode='median', device=None,
+                      mem_budget=None, stream=None, consistency=None):
+    """solve_tiles with one expected disparity per tile -> (match, q_eff), or (match, q_eff, err)
+    with ``consistency``.  ``prior``: int [T][2] (row, column), host or device -- a device prior
+    (tile_prior's) is never read on the host, so nothing synchronises between it and the solve.
+    Per chunk of solve_tiles' chunk loop the crops are packed (pack_tiles: img2's cut at origin -
+    prior, clamped into the image), the packed pair is solved by the unchanged path and the
+    matches are shifted into the frame of img1's tile (shift_matches), so that match[:, 1] is
+    the local match minus q_eff and cal_map / stitch give global disparities.  Packing per chunk
+    keeps the extra memory at one chunk's crops: two images of about T_chunk (h0 + ws - 1)
+    (w0 + ws - 1) bytes.  match: float64 [T][3][h0][w0]; q_eff: int32 [T][2], the priors that
+    took effect after the clamp.  ``consistency``: a tolerance in pixels; the packed pair is then
+    solved in both directions (solve_tiles_bidir) and checked per tile, in the local frames,
+    before the shift (fb_check): the cells that fail are NaN in rows 0 and 1 of match, err
+    [T][h0][w0] is the round-trip error.  A zero prior gives solve_tiles' tiles bit for bit."""
+    device = device or default_device()
+    tol = None if consistency is None else consistency_tol(consistency)
+    h0, w0 = _tile_shape(h0, w0)
+    org = _origins_host(origins)
+    T = len(org)
+    opts = (sub_pix, filtering, filter_window_size, filtering_num, filtering_mode)
+    with _on(stream):
+        a, b = to_device_u8(img1, device), to_device_u8(img2, device)
+        q = _prior_device(prior, T, device)
+        if mem_budget is None:
+            mem_budget = int(os.environ.get('DM_MEM_BUDGET', 64 << 30))
+        chunk = max(1, min(T, mem_budget // max(tile_bytes(h0, w0), 1)))
+        out = torch.empty((T, 3, h0, w0), dtype=torch.float64, device=device)
+        q_eff = torch.empty((T, 2), dtype=torch.int32, device=device)
+        err = torch.empty((T, h0, w0), dtype=torch.float64, device=device) if tol is not None else None
+        for s in range(0, T, chunk):
+            o = org[s:s + chunk]
+            p1, p2, _, qe = pack_tiles(a, b, o, q[s:s + chunk], h0, w0, ws, device=device)
+            grid = pack_grid(len(o), h0, w0, ws)[0]
+            if tol is None:
+                m = solve_tiles(p1, p2, grid, h0, w0, ws, method, *opts, device=device, mem_budget=mem_budget)
+            else:
+                fwd, bwd = solve_tiles_bidir(p1, p2, grid, h0, w0, ws, method, *opts, device=device,
+                                             mem_budget=mem_budget)
+                err[s:s + len(o)], m = fb_check(fwd, bwd, tol)
+            out[s:s + len(o)] = shift_matches(m, qe)
+            q_eff[s:s + len(o)] = qe
+            del p1, p2, m
+    return (out, q_eff) if tol is None else (out, q_eff, err)
+
+
+def coarse_params(coarse):
+    """The ``coarse=`` keyword of ImageCutSolver as (k, tol): an int k in [1, 4], the number of
+    half-resolution levels above the image, or ``(k, tol)`` with tol a real >= 0, the
+    forward-backward tolerance of the coarse levels in their own pixels (1.0 in the first form)."""
+    if isinstance(coarse, (tuple, list)):
+        if len(coarse) != 2:
+            raise ValueError('coarse must be a level count k, (k, tol) or None')
+        k, tol = coarse
+    else:
+        k, tol = coarse, 1.0
+    return (_int_in(k, 1, 4, 'coarse levels must be an int in [1, 4] (got %r)'),
+            _real_in(tol, 0.0, np.inf, 'coarse tol must be a real >= 0 (got %r)'))
+
+
+def prior_keyword(prior, ntiles):
+    """The ``prior=`` keyword of ImageCutSolver -> (kind, value): ('tiles', int64 array
+    [ntiles][2]) for a pair of ints (d2, d1) -- one expected ('elevation2', 'elevation') for every
+    tile -- or an int array [ntiles][2] in tile order; ('dense', float64 [2][H][W], array or
+    tensor) for a float map of the two planes at full resolution (tile_prior(scale=1) turns it
+    into tile priors)."""
+    if isinstance(prior, torch.Tensor):
+        if prior.dtype == torch.float64 and prior.dim() == 3 and prior.shape[0] == 2 and prior.numel():
+            return 'dense', prior
+        raise ValueError('a tensor prior must be a float64 map [2][H][W]')
+    q = np.asarray(prior)
+    if q.dtype.kind in 'iu':
+        if q.shape == (2,):
+            q = np.tile(q.reshape(1, 2), (ntiles, 1))
+        if q.shape != (ntiles, 2):
+            raise ValueError('an int prior must be (d2, d1) or an array [%d][2] in tile order (got shape %r)'
+                             % (ntiles, tuple(q.shape)))
+        if np.abs(q.astype(np.int64)).max() > 2 ** 30:
+            raise ValueError('prior must lie in [-2^30, 2^30]')
+        return 'tiles', q.astype(np.int64)
+    if q.dtype.kind == 'f' and q.ndim == 3 and q.shape[0] == 2 and q.size:
+        return 'dense', np.ascontiguousarray(q, dtype=np.float64)
+    raise ValueError('prior must be (d2, d1), an int array [%d][2] or a float map [2][H][W]' % ntiles)
+
+
+def coarse_grids(shape, image_size, stride, window_size, k):
+    """(tile counts, origins) of the levels 0 .. k of a coarse-to-fine solve: level j is the image
+    halved j times (downsample2), cut with the same image_size, stride and window_size by the
+    reference's floor rule (cut_grid).  ValueError if the coarsest level holds no tile."""
+    shapes = [(int(shape[0]) >> j, int(shape[1]) >> j) for j in range(k + 1)]
+    try:      # (the levels shrink: a tile at level k means one at every level)
+        return [cut_grid(shp, image_size, stride, window_size) for shp in reversed(shapes)][::-1]
+    except IndexError:
+        raise ValueError('coarse=%d: no tile at the coarsest level (its %d x %d image holds no %d x %d tile with '
+                         'window_size %d)' % (k, shapes[k][0], shapes[k][1], image_size[0], image_size[1],
+                                              window_size)) from None
+
+
+def solve_coarse_to_fine(img1, img2, image_size, stride, ws, method, coarse, sub_pix=True, filtering=False,
+                         filter_window_size=3, filtering_num=3, filtering_mode='median', device=None,
+                         mem_budget=None, stream=None, consistency=None, trace=None):
+    """The tiles of a pair solved with priors from half-resolution solves of the same pair ->
+    (match, q_eff, err or None, valid, n, origins): solve_tiles_prior's results for level 0, the
+    uint8 [T] flags of the tiles that measured their own prior (tile_prior) and the level-0 tile
+    grid (cut_grid).  ``coarse``: k or (k, tol) (coarse_params).  The procedure:
+      images L_0 .. L_k, each downsample2 of the one before; the same image_size, stride, ws,
+      matching and filtering arguments at every level (ValueError if L_k holds no tile);
+      level k is solved with prior 0; every level j >= 1 with consistency=tol, its masked matches
+      stitched by the overwriting stitch in modes ('elevation2', 'elevation') -- no merge, no
+      chain -- and level j - 1 takes its priors from that map by tile_prior(scale=2);
+      level 0 is solved with ``consistency`` (the caller's) and level 1's priors.
+    The reachable disparity doubles per level.  The priors stay on the device: nothing
+    synchronises between the levels.  ``trace``: a list that receives one dict per level solved,
+    coarsest first (level, img1, img2, n, origins, prior, q_eff, match, err, and for a coarse level
+    d_map, the stitched pair of planes): the stages' own outputs, for tests."""
+    device = device or default_device()
+    k, tol = coarse_params(coarse)
+    h0, w0 = int(image_size[0]), int(image_size[1])
+    e = int((ws - 1) / 2)
+    opts = (sub_pix, filtering, filter_window_size, filtering_num, filtering_mode)
+    with _on(stream):
+        imgs = [(to_device_u8(img1, device), to_device_u8(img2, device))]
+        if imgs[0][0].shape != imgs[0][1].shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        grids = coarse_grids(imgs[0][0].shape, image_size, stride, ws, k)
+        for _ in range(k):
+            imgs.append((downsample2(imgs[-1][0]), downsample2(imgs[-1][1])))
+        prior = torch.zeros((len(grids[k][1]), 2), dtype=torch.int32, device=device)
+        valid = None
+        org_dev = [origins_device(g[1], device) for g in grids[:k]]      # tile_prior's, uploaded ahead
+        for j in range(k, -1, -1):
+            n, org = grids[j]
+            res = solve_tiles_prior(imgs[j][0], imgs[j][1], org, prior, h0, w0, ws, method, *opts, device=device,
+                                    mem_budget=mem_budget, consistency=tol if j else consistency)
+            rec = dict(level=j, img1=imgs[j][0], img2=imgs[j][1], n=n, origins=org, prior=prior, q_eff=res[1],
+                       match=res[0], err=res[2] if len(res) > 2 else None)
+            if j:
+                d, _ = stitch(res[0], n, h0, w0, stride, ('elevation2', 'elevation'))
+                prior, valid = tile_prior(d[0], d[1], org_dev[j - 1], h0, w0, e, scale=2)
+                rec['d_map'] = d
+            if trace is not None:
+                trace.append(rec)
+    n, org = grids[0]
+    return res[0], res[1], (res[2] if len(res) > 2 else None), valid, n, org

@@ -41,7 +41,9 @@ class ImageCutSolver():
         median_weight=None,
         photo=None,
         refine=None,
-        refine_where='filled'
+        refine_where='filled',
+        prior=None,
+        coarse=None
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -58,6 +60,10 @@ class ImageCutSolver():
             from deepmatching_stereo_matching_amd.misc.Feature_value import Feature_value
             Feature_value(feature_name)  # prints + exits like the reference
 
+        if prior is not None and coarse is not None:
+            raise ValueError('prior= and coarse= cannot be combined: coarse= measures the priors itself')
+        if padding and (prior is not None or coarse is not None):
+            raise ValueError('padding=True is not supported with prior= / coarse=: the reference zeroes img2 there')
         if padding:
             self._padding()
 
@@ -105,6 +111,24 @@ class ImageCutSolver():
             setattr(self, name, getattr(self.chain, name))
         self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
         self.refine_score_map = self.refine_shift_map = None
+        # Disparity priors (engine.solve_tiles_prior): tile t's crop of img2 is cut at its origin minus
+        # the expected disparity, so that a match outside the tile's own window of img2 can be found.
+        #   prior: (d2, d1) ints, one expected ('elevation2', 'elevation') for every tile, in the units and
+        #       sign of d_map; an int array [n0 * n1][2] in tile order (j outer, i inner); or a float map
+        #       [2][H][W] of the two planes at full resolution, e.g. an earlier d_map (engine.tile_prior
+        #       with scale 1 turns it into tile priors)
+        #   coarse: k or (k, tol), 1 <= k <= 4: the priors come from k half-resolution solves of the same
+        #       pair (engine.solve_coarse_to_fine), each checked forward-backward at tol (default 1.0)
+        # prior_map is then the int32 [n0][n1][2] priors that took effect at level 0 (after the clamp of the
+        # crop into the image), prior_valid_map the bool [n0][n1] tiles that measured their own prior (all
+        # true for an int prior).  None (both): the reference's behaviour, bit for bit.
+        self.prior = engine.prior_keyword(prior, max(self.len[0], 0) * max(self.len[1], 0)) if prior is not None else None
+        self.coarse = engine.coarse_params(coarse) if coarse is not None else None
+        if (self.prior is not None or self.coarse is not None) and merge is not None and consistency is not None:
+            raise ValueError('merge= together with consistency= is not supported with prior= / coarse=: the merge '
+                             'checks both directions in one frame, the tiles of a prior are checked in their own')
+        self.prior_map = self.prior_valid_map = None
+        self._prior_dev = None
 
         self.log_flg = True
 
@@ -194,8 +218,11 @@ class ImageCutSolver():
                                              speckle=self.speckle, smooth=self.smooth,
                                              smooth_guide=self.smooth_guide, median=self.median,
                                              median_weight=self.median_weight, photo=self.photo,
-                                             refine=self.refine, refine_where=self.refine_where)
-        if self.merge is not None:
+                                             refine=self.refine, refine_where=self.refine_where,
+                                             prior=self.prior, coarse=self.coarse)
+        if self.prior is not None or self.coarse is not None:
+            maps = self._stitch_prior(args, n, origins)
+        elif self.merge is not None:
             if self.consistency is not None:
                 fwd, bwd = engine.solve_tiles_bidir(*args)
             else:
@@ -210,6 +237,38 @@ class ImageCutSolver():
             match = engine.solve_tiles(*args)
             maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
         return self.chain.run(maps, self.img1, self.img2, self.exclusive_pix, self.consistency, self.merge)
+
+    def _stitch_prior(self, args, n, origins):
+        """The stitched maps of a solve with priors (self.prior or self.coarse) -> the head of the chain's
+        layout.  Level 0 is engine.solve_tiles_prior: with self.consistency the tiles are checked per tile in
+        their local frames (engine.fb_check), then shifted, then stitched in one direction, and the error is
+        the overwriting stitch of the per-tile error; with self.merge the shifted tiles are merged as a
+        one-direction solve.  The effective priors stay on the device (self._prior_dev) until the maps are
+        fetched."""
+        img1, img2, _, h0, w0, ws, method = args[:7]
+        opts = args[7:]
+        if self.coarse is not None:
+            match, q_eff, err, valid, _, _ = engine.solve_coarse_to_fine(img1, img2, [h0, w0], self.stride, ws, method,
+                                                                         self.coarse, *opts,
+                                                                         consistency=self.consistency)
+        else:
+            kind, prior = self.prior
+            valid = None
+            if kind == 'dense':
+                d = torch.as_tensor(prior).to(engine.default_device())
+                prior, valid = engine.tile_prior(d[0], d[1], origins, h0, w0, self.exclusive_pix, scale=1)
+            res = engine.solve_tiles_prior(img1, img2, origins, prior, h0, w0, ws, method, *opts,
+                                           consistency=self.consistency)
+            match, q_eff, err = res[0], res[1], (res[2] if len(res) > 2 else None)
+        self._prior_dev = (q_eff, valid)
+        if self.merge is not None:
+            maps = engine.stitch_merge(match, None, n, h0, w0, self.stride, self.degree_map_mode, None, self.merge,
+                                       self.merge_min_count)
+            return tuple(m for m in maps if m is not None)
+        maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
+        if err is not None:      # the stitch of a tile's score row, fed with the error
+            maps += (engine.stitch(torch.stack([err, err, err], 1), n, h0, w0, self.stride, ['elevation'])[1],)
+        return maps
 
     # attribute: (entry of chain.Chain.layout, a uint8 mask that is kept as bool)
     _MAPS = {'d_map': ('d_map', False), 'out_map': ('out_map', False),
@@ -231,6 +290,12 @@ class ImageCutSolver():
             t = maps.get(name)      # absent: the stage is off; None: off rank 0 with tile_sharding(result='root')
             a = t.cpu().numpy() if t is not None else None
             setattr(self, attr, a.astype(bool) if mask and a is not None else a)
+        if self._prior_dev is not None:
+            q_eff, valid = self._prior_dev
+            n0, n1 = self.len
+            self.prior_map = np.ascontiguousarray(q_eff.cpu().numpy().reshape(n1, n0, 2).transpose(1, 0, 2))
+            self.prior_valid_map = np.ones((n0, n1), dtype=bool) if valid is None else \
+                np.ascontiguousarray(valid.cpu().numpy().astype(bool).reshape(n1, n0).T)
 
     def __call__(self):
         self._cut_and_pool()

@@ -386,7 +386,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
                         smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
                         medianer=None, photo=None, photoer=None, refine=None, refine_where='filled',
-                        refiner=None):
+                        refiner=None, prior=None, coarse=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -444,7 +444,12 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     photo tensors: (d_map, out_map[, err][, spread, count][, speckles][, holes][, refine score, refine
     shift][[, rejected], score]).  None: nothing changes.
     The stages after the stitch, their order and the layout of the tuple are chain.py's (its module
-    docstring states the order once); a hook replaces the device stage of its name there."""
+    docstring states the order once); a hook replaces the device stage of its name there.
+    ``prior``, ``coarse``: ImageCutSolver's disparity priors; not None raises ValueError -- the bands
+    solve their tiles at one origin in both images."""
+    for name, value in (('prior=', prior), ('coarse=', coarse)):
+        if value is not None:
+            raise ValueError('%s not supported with tile sharding' % name)
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
     post = chain.Chain(modes, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide, median=median,

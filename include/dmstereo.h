@@ -616,6 +616,71 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
                     double *d_score /* may be NULL */, int8_t *d_shift /* may be NULL */,
                     void *d_work, void *stream);
 
+/* ---- Disparity priors: offset img2 crops for the unchanged solver (dm_prior.hip) --------------
+ * Not in the reference, which cuts tile t at one origin o_t in img1 and img2: a cell whose match
+ * lies outside its own tile of img2 cannot be found, and the share of correct cells falls like
+ * 1 - |d| / S with the disparity d.  With an expected disparity q_t = (row, column) per tile, in
+ * the units and sign of d_map ('elevation2', 'elevation': cell minus match), the img2 crop is cut
+ * at o_t - q_t, which brings the disparity inside the tile back to about 0.  No kernel of the solve
+ * changes: dm_pack_tiles copies the crop pairs into a fresh image pair, the existing entries solve
+ * it at the grid's origins, dm_shift_matches moves the matches into the frame of img1's tile, so
+ * that dm_cal_map, dm_stitch and dm_stitch_merge give global disparities (local + q').
+ * dm_tile_prior takes the q_t from a map of the same pair, dm_downsample2 makes the
+ * half-resolution pair such a map can be solved on.  tests/test_prior.py restates all four in
+ * numpy; the kernels equal it bit for bit.  Nothing here allocates or synchronises.
+ *
+ * dm_downsample2: dst[y][x] = (s[2y][2x] + s[2y][2x+1] + s[2y+1][2x] + s[2y+1][2x+1] + 2) >> 2 for
+ * the (H / 2) x (W / 2) destination (integer division: an odd last row or column is dropped).
+ * Strides in bytes.  DM_ERR_ARG for a null pointer, H or W below 2, a stride below its width. */
+int dm_downsample2(const uint8_t *d_src, int64_t stride, int32_t H, int32_t W, uint8_t *d_dst,
+                   int64_t dst_stride, void *stream);
+
+/* d_row, d_col: float64 [Hc][Wc], the 'elevation2' and 'elevation' planes of a map whose cell
+ * (y, x) sits at pixel (y + e, x + e) of an image `scale` (1 or 2) times smaller than the one the
+ * T tiles (d_origins int32 [T][2], h0 x w0 cells) are cut from.  Tile t covers image rows first =
+ * o_y + e .. last = o_y + e + h0 - 1; its footprint rows are first / scale - e .. last / scale - e
+ * (integer division), each end clamped into [0, Hc - 1], columns alike -- a footprint wholly
+ * outside the map becomes its nearest edge row or column.  Over the footprint cells where BOTH
+ * planes are finite (the range test on the double), n of them, the lower median of each plane is
+ * its element (n - 1) / 2 in the order of the order-preserving key of the double
+ * (dm_median_filter's); q = rint(scale * median), ties to even, clamped to [-2^30, 2^30], as int32.
+ * d_valid[t] = 1 and d_q[t] = (q_row, q_col) for such a tile.  A tile with n = 0 has d_valid[t] = 0
+ * and takes, per component, the lower median of the q of the tiles with d_valid = 1, or 0 if there
+ * is none.  One workgroup per tile plus one small launch for the fallback; integer counting only,
+ * the result is the same from run to run.  DM_ERR_ARG for a null pointer, a side below 1, Hc Wc or
+ * h0 w0 above 2^31 - 1, h0 / w0 / e above 65536, e below 0, another scale. */
+int dm_tile_prior(const double *d_row, const double *d_col, int32_t Hc, int32_t Wc, const int32_t *d_origins,
+                  int32_t T, int32_t h0, int32_t w0, int32_t e, int32_t scale, int32_t *d_q, uint8_t *d_valid,
+                  void *stream);
+
+/* HOST function (no device work): the packed pair of T tiles.  A crop has ch = h0 + ws - 1 rows and
+ * cw = w0 + ws - 1 columns; crop t sits at row (t / grid_cols) * ch, column (t % grid_cols) * cw of a
+ * uint8 image of *Hp rows and *Wp columns, *Wp a multiple of 16 (the pitch of the packed images:
+ * they are contiguous).  DM_ERR_UNSUPPORTED for a batch it does not take (a side below 1, a crop
+ * side above 65536, a packed side above 2^30). */
+int dm_pack_plan(int32_t T, int32_t h0, int32_t w0, int32_t ws, int32_t *grid_cols, int32_t *Hp, int32_t *Wp);
+
+/* Crop t of img1 is cut at o_t (d_origins, int32 [T][2]), crop t of img2 at o_t - q_t (d_prior,
+ * int32 [T][2]) clamped per axis into [0, H - ch] / [0, W - cw], so every packed crop pixel is a
+ * real pixel; d_q_eff[t] = o_t - the clamped origin is the prior that took effect.  The crops go
+ * to dm_pack_plan's places in d_pack1 / d_pack2 (contiguous *Hp x *Wp, 16-byte aligned); the cells
+ * of the grid beyond T and the columns beyond grid_cols * cw are 0.  d_pack_origins (int32 [T][2])
+ * receives the crops' places: the packed pair with these origins is a dm_tiles batch whose tile t
+ * has exactly the two crops above.  The o_t must lie inside the image (the caller's check, as for
+ * dm_tiles; the kernel clamps them like the img2 origins, so it never reads outside).  DM_ERR_ARG
+ * for a null pointer, an image smaller than a crop or above 2^30 a side, a stride below W, a
+ * packed image that is not 16-byte aligned; DM_ERR_UNSUPPORTED as dm_pack_plan. */
+int dm_pack_tiles(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2, int64_t stride2, int32_t H,
+                  int32_t W, const int32_t *d_origins, const int32_t *d_prior, int32_t T, int32_t h0, int32_t w0,
+                  int32_t ws, uint8_t *d_pack1, uint8_t *d_pack2, int32_t *d_pack_origins, int32_t *d_q_eff,
+                  void *stream);
+
+/* In place on dm_match's output, float64 [T][3][h0][w0]: map[t][0] -= q_eff[t][0], map[t][1] -=
+ * q_eff[t][1] (one float64 subtraction of the converted integer: NaN stays NaN), the score row is
+ * not touched.  A match position of the packed solve, expressed in img2's offset crop, becomes a
+ * position in the frame of img1's tile; it may lie outside [0, h0) x [0, w0). */
+int dm_shift_matches(double *d_match, const int32_t *d_q_eff, int32_t T, int32_t h0, int32_t w0, void *stream);
+
 /* ----Gauss-Seidel post-processing (dm_postproc.hip) -------------
  * misc/optimize_loop.py (optimize_loop :15-37, image_threshold :40-44) and misc/opt_loop.py
  * (optimize_loop_bilateral_horizon :16-35, _vertical :39-58, make_weight :60-85).  Maps are
@@ -699,7 +764,8 @@ const char *dm_last_error(void);
  * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
  * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16,
- * dm_level_num_f16, dm_photo_bytes, dm_photo_score, dm_photo_refine_bytes and dm_photo_refine
+ * dm_level_num_f16, dm_photo_bytes, dm_photo_score, dm_photo_refine_bytes, dm_photo_refine,
+ * dm_downsample2, dm_tile_prior, dm_pack_plan, dm_pack_tiles and dm_shift_matches
  * are additive entries within 1.10:
  * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);

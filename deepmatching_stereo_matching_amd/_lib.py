@@ -108,6 +108,9 @@ SIGNATURES = {
     'dm_photo_refine_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_size_t),
     'dm_photo_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
                          ctypes.c_double, _I, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    'dm_lsm_refine_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_size_t),
+    'dm_lsm_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
+                       ctypes.c_double, _I, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     'dm_downsample2': ([_P, ctypes.c_int64, _I, _I, _P, ctypes.c_int64, _P], ctypes.c_int),
     'dm_tile_prior': ([_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P], ctypes.c_int),
     'dm_pack_plan': ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),

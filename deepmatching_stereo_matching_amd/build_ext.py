@@ -20,7 +20,7 @@ SOURCES = [os.path.join(CSRC, 'dm_kernels.hip'), os.path.join(CSRC, 'dm_postproc
            os.path.join(CSRC, 'dm_merge.hip'), os.path.join(CSRC, 'dm_speckle.hip'),
            os.path.join(CSRC, 'dm_bilateral.hip'), os.path.join(CSRC, 'dm_median.hip'),
            os.path.join(CSRC, 'dm_photo.hip'), os.path.join(CSRC, 'dm_photo_refine.hip'),
-           os.path.join(CSRC, 'dm_prior.hip')]
+           os.path.join(CSRC, 'dm_lsm.hip'), os.path.join(CSRC, 'dm_prior.hip')]
 DEPS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + \
     [os.path.join(REPO, 'include', 'dmstereo.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')

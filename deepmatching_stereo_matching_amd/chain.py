@@ -1,7 +1,7 @@
 """The post-processing chain of a stitched d_map, for ImageCutSolver and shard.solve_image_sharded.
 
-The chain is stitch -> median -> photo reject -> speckle -> fill -> refine -> smooth -> photo
-score (STAGES below is that order in code).  The caller stitches; every stage after that is
+The chain is stitch -> median -> photo reject -> speckle -> fill -> refine -> lsm -> smooth ->
+photo score (STAGES below is that order in code).  The caller stitches; every stage after that is
 optional, works on d_map [len(modes)][H][W] in place and is switched on by its keyword:
 
   median        engine.median_filter, all modes in one call, weighted by out_map when
@@ -13,13 +13,16 @@ optional, works on d_map [len(modes)][H][W] in place and is switched on by its k
   fill          engine.fill_holes; adds the uint8 mask `holes` of the cells that were filled.
   refine        engine.photo_refine on the two elevation planes, of the filled cells only with
                 refine_where='filled'; adds `refine_score` and the int8 `refine_shift`.
+  lsm           engine.lsm_refine on the two elevation planes: the least-squares sub-pixel
+                step, of the filled cells only with lsm_where='filled'; adds `lsm_score` and
+                the int8 `lsm_status`.
   smooth        engine.bilateral_filter, guided by img1 under the map's cells (smooth_guide
                 'image') or by the map itself ('self'); holes stay holes.
   photo score   with photo=: adds `score`, the photo-consistency of the final d_map.
 
 The result is a tuple in the order of Chain.layout -- not the order the stages run in:
 (d_map, out_map[, err][, spread, count][, speckles][, holes][, refine_score, refine_shift]
-[[, rejected], score]).  A stage may be replaced by a host function (the hooks of
+[, lsm_score, lsm_status][[, rejected], score]).  A stage may be replaced by a host function (the hooks of
 solve_image_sharded); the calls are the ones written in the stage functions below.
 """
 
@@ -86,6 +89,20 @@ def _refine(c, v, r):
                                                                               r.e, holes)
 
 
+def _lsm(c, v, r):
+    if c.lsm is None:
+        return
+    d = v['d_map']
+    holes = v['holes'] if c.lsm_where == 'filled' else None
+    if r.lsmer is not None:
+        row, col = engine.refine_planes(c.modes)
+        mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
+        d[row], d[col], v['lsm_score'], v['lsm_status'] = r.lsmer(
+            r.img1, r.img2, d[row], d[col], c.lsm[0], c.lsm[1], r.e, c.lsm[2], mask)
+    else:
+        v['d_map'], v['lsm_score'], v['lsm_status'] = engine.lsm_stage(r.img1, r.img2, d, c.modes, c.lsm, r.e, holes)
+
+
 def _smooth(c, v, r):
     if c.smooth is None:
         return
@@ -110,7 +127,7 @@ def _photo_score(c, v, r):
         v['score'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, False)
 
 
-STAGES = (_median, _photo_reject, _speckle, _fill, _refine, _smooth, _photo_score)
+STAGES = (_median, _photo_reject, _speckle, _fill, _refine, _lsm, _smooth, _photo_score)
 
 
 class Chain:
@@ -118,7 +135,7 @@ class Chain:
     parsed by engine.*_params: None switches a stage off."""
 
     def __init__(self, modes, fill=None, speckle=None, smooth=None, smooth_guide='image', median=None,
-                 median_weight=None, photo=None, refine=None, refine_where='filled'):
+                 median_weight=None, photo=None, refine=None, refine_where='filled', lsm=None, lsm_where='all'):
         self.modes = modes
         self.fill = engine.fill_iterations(fill) if fill is not None else None
         self.speckle = engine.speckle_params(speckle) if speckle is not None else None
@@ -138,6 +155,11 @@ class Chain:
         if self.refine is not None:
             engine.refine_planes(modes)
             engine.refine_where(refine_where, self.fill)
+        self.lsm = engine.lsm_params(lsm) if lsm is not None else None
+        self.lsm_where = lsm_where
+        if self.lsm is not None:
+            engine.refine_planes(modes)
+            engine.refine_where(lsm_where, self.fill, 'lsm_where')
 
     def layout(self, H, W, consistency, merge):
         """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
@@ -155,6 +177,8 @@ class Chain:
             lay.append(('holes', (M, H, W), u8))
         if self.refine is not None:
             lay += [('refine_score', (H, W), f64), ('refine_shift', (2, H, W), torch.int8)]
+        if self.lsm is not None:
+            lay += [('lsm_score', (H, W), f64), ('lsm_status', (H, W), torch.int8)]
         if self.photo is not None:
             if self.photo[1] is not None:
                 lay.append(('rejected', (H, W), u8))
@@ -166,7 +190,7 @@ class Chain:
         return [name for name, _, _ in self.layout(0, 0, consistency, merge)]
 
     def run(self, stitched, img1, img2, e, consistency, merge, medianer=None, photoer=None, speckler=None,
-            filler=None, refiner=None, smoother=None):
+            filler=None, refiner=None, smoother=None, lsmer=None):
         """The stages over ``stitched``, the tensors of the stitch: the head of the layout, a merge
         of one direction without its err -> the result tuple.  ``img1``, ``img2``: the pair as the
         caller got it (never the stacked one of a two-direction solve); ``e``: the offset of a map
@@ -174,7 +198,7 @@ class Chain:
         names = self.names(consistency, merge)
         v = dict(zip(names, stitched))
         r = SimpleNamespace(img1=img1, img2=img2, e=int(e), medianer=medianer, photoer=photoer, speckler=speckler,
-                            filler=filler, refiner=refiner, smoother=smoother)
+                            filler=filler, refiner=refiner, smoother=smoother, lsmer=lsmer)
         for stage in STAGES:
             stage(self, v, r)
         return tuple(v[name] for name in names)

@@ -32,23 +32,6 @@
 #define REF_SMAX 3
 #define REF_POSMAX 1073741824.0      // 2^30
 
-// the first nbytes (4 .. 4 NW) bytes at p as NW little-endian dwords, zero from nbytes on.  Reads
-// nothing outside [p, p + nbytes).
-template <int NW>
-__device__ __forceinline__ void ref_row(const uint8_t *p, int nbytes, uint32_t (&d)[NW])
-{
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-        const int left = nbytes - 4 * k;      // bytes of the row from dword k on
-        if (left >= 4)
-            d[k] = pho_ld4(p + 4 * k);
-        else if (left > 0)
-            d[k] = pho_ld4(p + nbytes - 4) >> (8 * (4 - left));
-        else
-            d[k] = 0u;
-    }
-}
-
 // dm_photo_score's rule 5 on the exact sums of one candidate (include/dmstereo.h)
 __device__ __forceinline__ double ref_tail(int64_t n, int64_t Sa, double VA, double w0, double w1, double w2, double w3,
                                            uint32_t S0, uint32_t S1, uint32_t S2, uint32_t S3, uint32_t A0, uint32_t A1,
@@ -173,7 +156,7 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
                 for (int k = 0; k < ND; ++k) ap[k] = 0;
                 for (int q = 0; q <= D; ++q) {
                     uint32_t raw[NW], Wc[K][ND], ac[ND];
-                    ref_row<NW>(pb + (size_t)q * stride2, nbytes, raw);
+                    pho_rowz<NW>(pb + (size_t)q * stride2, nbytes, raw);
 #pragma unroll
                     for (int j = 0; j < K; ++j) {
 #pragma unroll

@@ -682,7 +682,7 @@ def stitch(match, n, h0, w0, stride, modes, stream=None):
     return dmap, score
 
 
-# ---- argument plumbing of the d_map stages below (fill_holes ... photo_refine) -------------------
+# ---- argument plumbing of the d_map stages below (fill_holes ... lsm_refine) -------------------
 def _int_in(x, lo, hi, msg, got=None):
     """int(x) of an int (not a bool) in [lo, hi]; else ValueError(msg % (got or x,))."""
     if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
@@ -1115,13 +1115,13 @@ def refine_planes(modes):
     return photo_planes(modes)
 
 
-def refine_where(where, fill):
-    """The ``refine_where=`` keyword: 'filled' (only the cells the fill produced; needs ``fill=``) or
-    'all'."""
+def refine_where(where, fill, keyword='refine_where'):
+    """The ``refine_where=`` keyword, and ``lsm_where=`` under its own name: 'filled' (only the cells
+    the fill produced; needs ``fill=``) or 'all'."""
     if where not in ('filled', 'all'):
-        raise ValueError("refine_where must be 'filled' or 'all'")
+        raise ValueError("%s must be 'filled' or 'all'" % keyword)
     if where == 'filled' and fill is None:
-        raise ValueError("refine_where='filled' needs fill=")
+        raise ValueError("%s='filled' needs fill=" % keyword)
     return where
 
 
@@ -1189,6 +1189,87 @@ def refine_stage(img1, img2, d_map, modes, refine, offset, holes=None):
                                               min_gain=refine[2], mask=mask, out=(d_map[ir], d_map[ic]),
                                               return_score=True, return_shift=True)
     return d_map, score, shift
+
+
+def lsm_params(lsm):
+    """The ``lsm=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius, iters,
+    max_move): ``(radius, iters)`` or ``(radius, iters, max_move)`` with an int radius in [1, 7]
+    (the window is (2 radius + 1)^2 pixels), an int iters in [1, 8] (the least-squares steps) and
+    max_move a real in (0, 2] (1.0 in the first form): a cell whose position leaves the square of
+    that half-side around its start keeps its input."""
+    if not isinstance(lsm, (tuple, list)) or len(lsm) not in (2, 3):
+        raise ValueError('lsm must be (radius, iters), (radius, iters, max_move) or None')
+    radius, iters = lsm[0], lsm[1]
+    max_move = lsm[2] if len(lsm) == 3 else 1.0
+    return (_int_in(radius, 1, 7, 'lsm radius must be an int in [1, 7] (got %r)'),
+            _int_in(iters, 1, 8, 'lsm iters must be an int in [1, 8] (got %r)'),
+            _real_in(max_move, 0.0, 2.0, 'lsm max_move must be a real in (0, 2] (got %r)', open_lo=True))
+
+
+def lsm_refine(img1, img2, d_row, d_col, radius, iters, offset=0, max_move=1.0, mask=None, out=None,
+               return_score=False, return_status=False, stream=None):
+    """Least-squares sub-pixel matching of a disparity map (dm_lsm_refine).  Images, planes,
+    ``offset`` and ``radius`` as in photo_score.  Every cell linearises img1 around its window and
+    solves ``iters`` times, iters in [1, 8], for the shift that best explains the window by img2
+    resampled at the current position, gain and offset free; the new position is kept if
+    photo_score's correlation there is strictly higher than at the start and no step left the
+    square of half-side ``max_move`` (a real in (0, 2]) around the start or the image.  Every other
+    cell keeps its bits.  ``mask``: a uint8 or bool tensor [H][W] on the planes' device; only the
+    cells where it is not 0 are refined.  ``out``: a pair of contiguous float64 tensors [H][W] for
+    the two planes (``out=(d_row, d_col)`` works in place when they are contiguous), else new
+    tensors.
+    -> (d_row', d_col'); then, when asked for, the float64 score (of the new position of an
+    accepted cell, else of the start; NaN for a cell that was not scored) and the int8 status
+    [H][W] are appended: ``iters`` accepted, 0 skipped, -1 no texture (a singular system or a flat
+    patch), -2 left the image or the square, -3 not better."""
+    dev = _planes_device(d_row, d_col)
+    radius, iters, max_move = lsm_params((radius, iters, max_move))
+    oy, ox = _offset(offset)
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
+                mask.shape == d_row.shape):
+            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
+                o.shape == d_row.shape and o.is_contiguous() for o in out)):
+            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
+    H, W = d_row.shape
+    with _on(stream):
+        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
+                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
+        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
+        status = torch.empty((H, W), dtype=torch.int8, device=dev) if return_status else None
+        if H and W:
+            if not a.numel():
+                raise ValueError('empty image')
+            lib = L.load()
+            work = _workspace(lib.dm_lsm_refine_bytes(a.shape[0], a.shape[1], H, W, radius, iters), dev,
+                              'lsm_refine does not take %d x %d cells on a %d x %d image' %
+                              (H, W, a.shape[0], a.shape[1]))
+            m = None if mask is None else mask.to(torch.uint8).contiguous()
+            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
+            L.check(lib.dm_lsm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
+                                      L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                      radius, iters, max_move, 0, L.ptr(m), L.ptr(o_row), L.ptr(o_col),
+                                      L.ptr(score), L.ptr(status), L.ptr(work), L.stream_handle()), 'dm_lsm_refine')
+    return (o_row, o_col) + ((score,) if return_score else ()) + ((status,) if return_status else ())
+
+
+def lsm_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
+    """The ``lsm=`` stage of the chain on the stitched d_map [len(modes)][H][W], in place, after the
+    refine stage and before the smoothing.  ``holes``: the fill's uint8 mask [len(modes)][H][W] --
+    only the cells that were filled in the row or in the column plane are matched
+    (lsm_where='filled') -- or None: every cell.  -> (d_map, score, int8 status [H][W])."""
+    ir, ic = refine_planes(modes)
+    mask = None if holes is None else (holes[ir] | holes[ic])
+    d_row, d_col, score, status = lsm_refine(img1, img2, d_map[ir], d_map[ic], lsm[0], lsm[1], offset=offset,
+                                             max_move=lsm[2], mask=mask, out=(d_map[ir], d_map[ic]),
+                                             return_score=True, return_status=True)
+    return d_map, score, status
 
 
 # ---- disparity priors (csrc/dm_prior.hip; include/dmstereo.h has the definitions) ----------------

@@ -43,7 +43,9 @@ class ImageCutSolver():
         refine=None,
         refine_where='filled',
         prior=None,
-        coarse=None
+        coarse=None,
+        lsm=None,
+        lsm_where='all'
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -103,14 +105,20 @@ class ImageCutSolver():
         #       refine_where: 'filled' (only the cells the fill produced; needs fill=) or 'all'.  Needs
         #       'elevation' and 'elevation2' and no 'distance' in degree_map_mode.  refine_score_map is the
         #       score of the position kept (NaN: not refined), refine_shift_map the int8 shift [2][H][W]
+        #   lsm: (radius, iters) or (radius, iters, max_move) of the least-squares sub-pixel matching after
+        #       the refine stage: a cell solves iters times for the shift that best explains its img1 window
+        #       and keeps it if the photo-consistency score rises.  lsm_where: 'all' or 'filled' (needs
+        #       fill=).  The modes as for refine.  lsm_score_map is the score of the position kept (NaN: not
+        #       scored), lsm_status_map the int8 status [H][W] (iters: accepted, 0: skipped, < 0: kept)
         self.chain = chain.Chain(degree_map_mode, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide,
                                  median=median, median_weight=median_weight, photo=photo, refine=refine,
-                                 refine_where=refine_where)
+                                 refine_where=refine_where, lsm=lsm, lsm_where=lsm_where)
         for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
-                     'refine_where'):
+                     'refine_where', 'lsm', 'lsm_where'):
             setattr(self, name, getattr(self.chain, name))
         self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
         self.refine_score_map = self.refine_shift_map = None
+        self.lsm_score_map = self.lsm_status_map = None
         # Disparity priors (engine.solve_tiles_prior): tile t's crop of img2 is cut at its origin minus
         # the expected disparity, so that a match outside the tile's own window of img2 can be found.
         #   prior: (d2, d1) ints, one expected ('elevation2', 'elevation') for every tile, in the units and
@@ -193,7 +201,7 @@ class ImageCutSolver():
         With self.merge set the stitch is engine.stitch_merge (both directions when
         self.consistency is set) and the spread and the uint8 count of valid candidates follow
         out_map / the error.  The stitched d_map then runs through self.chain (chain.py: the stages
-        that self.fill, self.speckle, self.smooth, self.median, self.photo and self.refine switch on,
+        that self.fill, self.speckle, self.smooth, self.median, self.photo, self.refine and self.lsm switch on,
         against self.img1 / self.img2 with e = exclusive_pix), which appends the tensors of its
         stages: the tuple is the one chain.Chain.layout names."""
         from deepmatching_stereo_matching_amd import shard
@@ -219,6 +227,7 @@ class ImageCutSolver():
                                              smooth_guide=self.smooth_guide, median=self.median,
                                              median_weight=self.median_weight, photo=self.photo,
                                              refine=self.refine, refine_where=self.refine_where,
+                                             lsm=self.lsm, lsm_where=self.lsm_where,
                                              prior=self.prior, coarse=self.coarse)
         if self.prior is not None or self.coarse is not None:
             maps = self._stitch_prior(args, n, origins)
@@ -278,6 +287,7 @@ class ImageCutSolver():
              'speckle_map': ('speckles', True),        # the cells the speckle filter removed (before any fill)
              'hole_map': ('holes', True),              # d_map is dense; the cells that were filled
              'refine_score_map': ('refine_score', False), 'refine_shift_map': ('refine_shift', False),
+             'lsm_score_map': ('lsm_score', False), 'lsm_status_map': ('lsm_status', False),
              'photo_reject_map': ('rejected', True),   # the cells scoring below min_score (before any fill)
              'photo_map': ('score', False)}
 

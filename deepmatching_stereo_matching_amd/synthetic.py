@@ -61,6 +61,20 @@ def stereo_pair(h, w, seed=0, dx=2, max_disp=None, sinusoidal=False):
     return img1, img2
 
 
+def subpixel_pair(h, w, seed, ky, kx, up=4):
+    """Return (img1, img2), uint8 (h, w), with a known sub-pixel shift: the texture is generated
+    at ``up`` times the resolution with sigma = up, img1 is every up-th pixel of it from phase
+    (0, 0) and img2 every up-th pixel from phase (ky, kx), 0 <= ky, kx < up.  So img2(y, x) =
+    img1(y + ky / up, x + kx / up): the match of img1's pixel lies ky / up rows and kx / up columns
+    before it, and the true d_map is +ky / up in 'elevation2' and +kx / up in 'elevation'."""
+    if not (0 <= ky < up and 0 <= kx < up):
+        raise ValueError('the phase (ky, kx) must lie in [0, up)')
+    tex = texture(up * (h + 1), up * (w + 1), seed, sigma=float(up))
+    img1 = tex[0:up * h:up, 0:up * w:up].copy()
+    img2 = tex[ky:ky + up * h:up, kx:kx + up * w:up].copy()
+    return img1, img2
+
+
 CONTENT_KINDS = ('binary', 'identical', 'dark', 'bright', 'dark_bright', 'low4', 'high4',
                  'checker', 'stripes', 'edge', 'const')
 

@@ -616,6 +616,75 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
                     double *d_score /* may be NULL */, int8_t *d_shift /* may be NULL */,
                     void *d_work, void *stream);
 
+/* ---- Least-squares sub-pixel matching of a disparity map (dm_lsm.hip) -----------------------
+ * Not in the reference.  Every other stage moves a cell on the integer grid or interpolates it;
+ * dm_lsm_refine measures the sub-pixel part: least-squares matching (Gruen 1985; the
+ * Lucas-Kanade step) linearises img1 around the cell's window and solves, `iters` times, for the
+ * shift that best explains the window by img2 resampled at the current position, gain and offset
+ * left free.  Images, planes, offsets and the radius r in [1, 7] are dm_photo_score's; iters in
+ * [1, 8], max_move a real in (0, 2].  cy, cx, py, px, iy, ix, fy, fx, A, P0..P3, n, sa, saa, S_k,
+ * CA_k, CB_kl, VA, w0..w3, num, vb and "the score at a position" are dm_photo_score's rules 2-5
+ * (rule 5 operation for operation); float64 throughout, one rounding per operation, no
+ * contraction.  Per cell (y, x):
+ *   1. The cell is skipped if d_mask is given and 0 at the cell, if d_row or d_col is not finite
+ *      (dm_photo_score's rule 1), or if the img1 window with a one-pixel halo leaves the image:
+ *      not (r+1 <= cy <= Hi-r-2 and r+1 <= cx <= Wi-r-2).  A skipped cell has status 0, the score
+ *      NaN (0x7ff8000000000000), and copies both planes bit for bit.
+ *   2. Once per cell, as exact integers over the window's taps (i, j): Gx(i,j) = A(i,j+1) -
+ *      A(i,j-1), Gy(i,j) = A(i+1,j) - A(i-1,j) (doubled central differences, read from the halo),
+ *        gx = sum Gx, gy = sum Gy,
+ *        Hxx = n sum(Gx^2) - gx^2, Hyy = n sum(Gy^2) - gy^2, Hxy = n sum(Gx Gy) - gx gy,
+ *        RAx = n sum(Gx A) - gx sa, RAy = n sum(Gy A) - gy sa.
+ *      Each is below 2^53 in magnitude and converts to double exactly.  D = Hxx * Hyy - Hxy * Hxy
+ *      in double (the products exceed int64 at r = 7).  Unless D > 0: status -1, the score NaN,
+ *      the input is kept.
+ *   3. (py0, px0) = ((double)cy - d_row, (double)cx - d_col).  If it fails dm_photo_score's rule
+ *      3 (r <= py0 < Hi-r-1 and r <= px0 < Wi-r-1, tested on the double): status -2, the score
+ *      NaN, the input is kept.  Else s0 is the score at (py0, px0).
+ *   4. Step t = 1 .. iters from the current (py, px), which starts at (py0, px0): with the integer
+ *      sums of dm_photo_score's rule 4 at this position and, for k = 0..3,
+ *        GX_k = n sum(Gx P_k) - gx S_k,   GY_k = n sum(Gy P_k) - gy S_k
+ *      (exact, converted to double), num and vb as in rule 5 there.  Unless vb > 0: status -1, the
+ *      input is kept.  Else
+ *        gbx = ((w0 GX_0 + w1 GX_1) + w2 GX_2) + w3 GX_3,   gby likewise with GY_k
+ *        alpha = num / vb
+ *        bx = RAx - alpha * gbx,   by = RAy - alpha * gby
+ *        ux = ((Hyy * bx) - (Hxy * by)) / D,   uy = ((Hxx * by) - (Hxy * bx)) / D
+ *        px = px + 2.0 * ux,   py = py + 2.0 * uy
+ *      Unless |py - py0| <= max_move and |px - px0| <= max_move and the new position passes rule
+ *      3 of dm_photo_score (a NaN fails): status -2, the input is kept.
+ *   5. s1 is the score at the final position.  s1 > s0: the cell is accepted, status = iters,
+ *      out_row = (double)cy - py, out_col = (double)cx - px, the score is s1.  Else status -3, the
+ *      input bits are kept, the score is s0.  A cell that ended with -1 or -2 in rule 4 has the
+ *      score s0.
+ *   6. A cell reads only its own d_row and d_col, before it writes: d_out_row and d_out_col may
+ *      alias d_row and d_col.  The result depends on nothing but the cell.
+ * The factor 2.0 undoes the doubling of the differences: with g = G / 2 the normal equations are
+ * (H / 4) u' = b / 2.  It follows that a cell on identical windows at an integer disparity has
+ * alpha = 1.0, bx = by = 0.0 and status -3 (it never moves), that an accepted cell scores
+ * strictly above dm_photo_score of the input, and that an unaccepted scored cell reports
+ * dm_photo_score's bits.  tests/test_lsm_host.py restates this in plain loops; the kernel equals
+ * it bit for bit. */
+
+/* Bytes of the workspace dm_lsm_refine asks for (a constant 16: the kernel keeps everything on
+ * chip); 0 for a shape it does not take: dm_photo_bytes' limits on H, W, Hi or Wi above 2^30, a
+ * radius outside [1, 7] or iters outside [1, 8]. */
+size_t dm_lsm_refine_bytes(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t iters);
+
+/* d_mask (uint8 [H][W]), d_score (float64 [H][W]) and d_status (int8 [H][W]) may be NULL.  d_work:
+ * dm_lsm_refine_bytes(...) bytes, not NULL.  flags must be 0.  DM_ERR_ARG for a null image /
+ * plane / output / workspace, a side below 1, a stride below Wi, an offset outside [-2^30, 2^30],
+ * a radius outside [1, 7], iters outside [1, 8], a max_move outside (0, 2] (NaN included), a flag
+ * bit; DM_ERR_UNSUPPORTED for the other shapes dm_lsm_refine_bytes refuses.  Validation precedes
+ * every HIP call; nothing is allocated, nothing synchronises, one launch on `stream`; the result
+ * is the same from run to run. */
+int dm_lsm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2, int64_t stride2,
+                  int32_t Hi, int32_t Wi, const double *d_row, const double *d_col, int32_t H, int32_t W,
+                  int32_t oy, int32_t ox, int32_t radius, int32_t iters, double max_move, int32_t flags,
+                  const uint8_t *d_mask /* may be NULL */, double *d_out_row, double *d_out_col,
+                  double *d_score /* may be NULL */, int8_t *d_status /* may be NULL */,
+                  void *d_work, void *stream);
+
 /* ---- Disparity priors: offset img2 crops for the unchanged solver (dm_prior.hip) --------------
  * Not in the reference, which cuts tile t at one origin o_t in img1 and img2: a cell whose match
  * lies outside its own tile of img2 cannot be found, and the share of correct cells falls like
@@ -765,7 +834,7 @@ const char *dm_last_error(void);
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
  * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16,
  * dm_level_num_f16, dm_photo_bytes, dm_photo_score, dm_photo_refine_bytes, dm_photo_refine,
- * dm_downsample2, dm_tile_prior, dm_pack_plan, dm_pack_tiles and dm_shift_matches
+ * dm_lsm_refine_bytes, dm_lsm_refine, dm_downsample2, dm_tile_prior, dm_pack_plan, dm_pack_tiles and dm_shift_matches
  * are additive entries within 1.10:
  * no existing entry, struct or workspace changed, so the version stays 110. */
 int dm_abi_version(void);

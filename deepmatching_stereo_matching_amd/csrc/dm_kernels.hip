@@ -1914,6 +1914,8 @@ static int volume_f32(const dm_tiles *b, void *d_stats, float *d_l0, void *strea
     int rc = check_tiles(b);
     if (rc) return rc;
     if (!d_stats || !d_l0) return dm_fail(DM_ERR_ARG, "null workspace / output");
+    // the MFMA volume kernels store 16 bytes per lane (k_volume_ls, k_volume_mfq)
+    if ((uintptr_t)d_l0 & 15) return dm_fail(DM_ERR_ARG, "the level-0 volume must be 16-byte aligned (got %p)", (void *)d_l0);
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     dim3 grid(P, b->T);
@@ -1935,6 +1937,8 @@ static int volume_f16(const dm_tiles *b, void *d_stats, uint16_t *d_l0, void *st
     int rc = check_tiles(b);
     if (rc) return rc;
     if (!d_stats || !d_l0) return dm_fail(DM_ERR_ARG, "null workspace / output");
+    // the MFMA volume kernels store 16 bytes per lane (k_volume_ls, k_volume_mfq)
+    if ((uintptr_t)d_l0 & 15) return dm_fail(DM_ERR_ARG, "the level-0 volume must be 16-byte aligned (got %p)", (void *)d_l0);
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     _Float16 *out = (_Float16 *)d_l0;

@@ -99,7 +99,9 @@ int dm_corr_level12(const dm_tiles *b, void *d_stats, double *d_level1, double *
 
 /* Materialise the level-0 min-max volume "co_map" (float32 [T][P][P]) and the per-patch
  * min/max.  Replaces _create_simple_initial_co_map (:69-87) for callers that read
- * co_map directly (bad_matching.py:62-70).  Needs dm_corr_stats first. */
+ * co_map directly (bad_matching.py:62-70).  Needs dm_corr_stats first.  d_l0 must be 16-byte
+ * aligned, here and in dm_corr_volume_f16 and dm_corr_volume_ex (the MFMA kernels store 16 bytes
+ * per lane): DM_ERR_ARG otherwise, before any HIP call. */
 int dm_corr_volume(const dm_tiles *b, void *d_stats, float *d_l0, void *stream);
 
 /* dm_corr_volume with a binary16 volume (uint16_t bit patterns, [T][P][P]): each float32

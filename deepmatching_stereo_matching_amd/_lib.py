@@ -17,6 +17,7 @@ import torch  # noqa: F401  (must precede the CDLL load, see module docstring)
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DM_LIB_PATH') or os.path.join(HERE, 'libdmstereo.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'dmstereo.h')
+HEADER_SGM = os.path.join(os.path.dirname(HERE), 'include', 'dmstereo_sgm.h')   # dm_sgm_refine: a header of its own
 
 DM_OK, DM_ERR_ARG, DM_ERR_SHAPE, DM_ERR_UNSUPPORTED, DM_ERR_HIP = 0, -1, -2, -3, -4
 DM_VOLUME_F16, DM_VOLUME_MINMAX_KNOWN = 1, 2   # dm_corr_volume_ex flags
@@ -33,6 +34,7 @@ DM_BILAT_FILL, DM_BILAT_GUIDE_U8 = 1, 2   # dm_bilateral_filter flags
 DM_MEDIAN_FILL = 1   # dm_median_filter flag
 DM_PHOTO_REJECT = 1   # dm_photo_score flag
 DM_REFINE_SUBPIX = 1   # dm_photo_refine flag
+DM_SGM_SUBPIX = 1   # dm_sgm_refine flag
 
 
 class DmUnavailable(ImportError):
@@ -111,6 +113,9 @@ SIGNATURES = {
     'dm_lsm_refine_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_size_t),
     'dm_lsm_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
                        ctypes.c_double, _I, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    'dm_sgm_bytes': ([_I, _I, _I, _I], ctypes.c_size_t),
+    'dm_sgm_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
+                       _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     'dm_downsample2': ([_P, ctypes.c_int64, _I, _I, _P, ctypes.c_int64, _P], ctypes.c_int),
     'dm_tile_prior': ([_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P], ctypes.c_int),
     'dm_pack_plan': ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
@@ -123,9 +128,9 @@ SIGNATURES = {
 _lib = None
 
 
-def header_symbols():
-    """Function names declared in include/dmstereo.h."""
-    txt = open(HEADER).read()
+def header_symbols(header=HEADER):
+    """Function names declared in include/dmstereo.h (or in ``header``)."""
+    txt = open(header).read()
     txt = re.sub(r'/\*.*?\*/', '', txt, flags=re.S)
     return sorted(set(re.findall(r'\b(dm_[a-z0-9_]+)\s*\(', txt)))
 

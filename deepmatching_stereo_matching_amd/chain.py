@@ -1,7 +1,7 @@
 """The post-processing chain of a stitched d_map, for ImageCutSolver and shard.solve_image_sharded.
 
-The chain is stitch -> median -> photo reject -> speckle -> fill -> refine -> lsm -> smooth ->
-photo score (STAGES below is that order in code).  The caller stitches; every stage after that is
+The chain is stitch -> median -> photo reject -> speckle -> fill -> sgm -> refine -> lsm -> smooth
+-> photo score (STAGES below is that order in code).  The caller stitches; every stage after that is
 optional, works on d_map [len(modes)][H][W] in place and is switched on by its keyword:
 
   median        engine.median_filter, all modes in one call, weighted by out_map when
@@ -11,6 +11,10 @@ optional, works on d_map [len(modes)][H][W] in place and is switched on by its k
                 min_score become NaN in every mode; adds the uint8 mask `rejected`.
   speckle       engine.filter_speckles; adds the uint8 mask `speckles` of the cells removed.
   fill          engine.fill_holes; adds the uint8 mask `holes` of the cells that were filled.
+  sgm           engine.sgm_refine on the two elevation planes: the cells are matched again
+                together, the candidates' costs and a smoothness term minimised along scan lines;
+                with sgm_where='filled' only the filled cells move and every other cell is an
+                anchor; adds `sgm_score` and the int8 `sgm_shift`.
   refine        engine.photo_refine on the two elevation planes, of the filled cells only with
                 refine_where='filled'; adds `refine_score` and the int8 `refine_shift`.
   lsm           engine.lsm_refine on the two elevation planes: the least-squares sub-pixel
@@ -21,9 +25,10 @@ optional, works on d_map [len(modes)][H][W] in place and is switched on by its k
   photo score   with photo=: adds `score`, the photo-consistency of the final d_map.
 
 The result is a tuple in the order of Chain.layout -- not the order the stages run in:
-(d_map, out_map[, err][, spread, count][, speckles][, holes][, refine_score, refine_shift]
-[, lsm_score, lsm_status][[, rejected], score]).  A stage may be replaced by a host function (the hooks of
-solve_image_sharded); the calls are the ones written in the stage functions below.
+(d_map, out_map[, err][, spread, count][, speckles][, holes][, sgm_score, sgm_shift]
+[, refine_score, refine_shift][, lsm_score, lsm_status][[, rejected], score]).  A stage may be
+replaced by a host function (the hooks of solve_image_sharded); the calls are the ones written in
+the stage functions below.
 """
 
 from types import SimpleNamespace
@@ -72,6 +77,20 @@ def _fill(c, v, r):
         v['d_map'], v['holes'] = r.filler(v['d_map'], c.fill)
     else:
         v['d_map'], v['holes'] = engine.fill_holes(v['d_map'], c.fill, out=v['d_map'], return_holes=True)
+
+
+def _sgm(c, v, r):
+    if c.sgm is None:
+        return
+    d = v['d_map']
+    holes = v['holes'] if c.sgm_where == 'filled' else None
+    if r.sgmer is not None:
+        row, col = engine.refine_planes(c.modes)
+        mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
+        d[row], d[col], v['sgm_score'], v['sgm_shift'] = r.sgmer(
+            r.img1, r.img2, d[row], d[col], c.sgm[0], c.sgm[1], r.e, c.sgm[2], c.sgm[3], c.sgm[4], mask)
+    else:
+        v['d_map'], v['sgm_score'], v['sgm_shift'] = engine.sgm_stage(r.img1, r.img2, d, c.modes, c.sgm, r.e, holes)
 
 
 def _refine(c, v, r):
@@ -127,7 +146,7 @@ def _photo_score(c, v, r):
         v['score'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, False)
 
 
-STAGES = (_median, _photo_reject, _speckle, _fill, _refine, _lsm, _smooth, _photo_score)
+STAGES = (_median, _photo_reject, _speckle, _fill, _sgm, _refine, _lsm, _smooth, _photo_score)
 
 
 class Chain:
@@ -135,7 +154,8 @@ class Chain:
     parsed by engine.*_params: None switches a stage off."""
 
     def __init__(self, modes, fill=None, speckle=None, smooth=None, smooth_guide='image', median=None,
-                 median_weight=None, photo=None, refine=None, refine_where='filled', lsm=None, lsm_where='all'):
+                 median_weight=None, photo=None, refine=None, refine_where='filled', lsm=None, lsm_where='all',
+                 sgm=None, sgm_where='all'):
         self.modes = modes
         self.fill = engine.fill_iterations(fill) if fill is not None else None
         self.speckle = engine.speckle_params(speckle) if speckle is not None else None
@@ -160,6 +180,11 @@ class Chain:
         if self.lsm is not None:
             engine.refine_planes(modes)
             engine.refine_where(lsm_where, self.fill, 'lsm_where')
+        self.sgm = engine.sgm_params(sgm) if sgm is not None else None
+        self.sgm_where = sgm_where
+        if self.sgm is not None:
+            engine.refine_planes(modes)
+            engine.refine_where(sgm_where, self.fill, 'sgm_where')
 
     def layout(self, H, W, consistency, merge):
         """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
@@ -175,6 +200,8 @@ class Chain:
             lay.append(('speckles', (M, H, W), u8))
         if self.fill is not None:
             lay.append(('holes', (M, H, W), u8))
+        if self.sgm is not None:
+            lay += [('sgm_score', (H, W), f64), ('sgm_shift', (2, H, W), torch.int8)]
         if self.refine is not None:
             lay += [('refine_score', (H, W), f64), ('refine_shift', (2, H, W), torch.int8)]
         if self.lsm is not None:
@@ -190,7 +217,7 @@ class Chain:
         return [name for name, _, _ in self.layout(0, 0, consistency, merge)]
 
     def run(self, stitched, img1, img2, e, consistency, merge, medianer=None, photoer=None, speckler=None,
-            filler=None, refiner=None, smoother=None, lsmer=None):
+            filler=None, refiner=None, smoother=None, lsmer=None, sgmer=None):
         """The stages over ``stitched``, the tensors of the stitch: the head of the layout, a merge
         of one direction without its err -> the result tuple.  ``img1``, ``img2``: the pair as the
         caller got it (never the stacked one of a two-direction solve); ``e``: the offset of a map
@@ -198,7 +225,7 @@ class Chain:
         names = self.names(consistency, merge)
         v = dict(zip(names, stitched))
         r = SimpleNamespace(img1=img1, img2=img2, e=int(e), medianer=medianer, photoer=photoer, speckler=speckler,
-                            filler=filler, refiner=refiner, smoother=smoother, lsmer=lsmer)
+                            filler=filler, refiner=refiner, smoother=smoother, lsmer=lsmer, sgmer=sgmer)
         for stage in STAGES:
             stage(self, v, r)
         return tuple(v[name] for name in names)

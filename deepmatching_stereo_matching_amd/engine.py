@@ -1272,6 +1272,96 @@ def lsm_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
     return d_map, score, status
 
 
+def sgm_params(sgm):
+    """The ``sgm=`` keyword of ImageCutSolver / shard.solve_image_sharded as (radius, search, p1, p2,
+    paths): ``(radius, search, p1, p2)`` or ``(radius, search, p1, p2, paths)`` with an int radius in
+    [1, 7] (the window is (2 radius + 1)^2 pixels), an int search in [1, 3] (the labels are the
+    (2 search + 1)^2 integer neighbours), the penalties p1 <= p2 for a step of one pixel and of more
+    between neighbouring cells, reals in [0, 16] in units of the score, returned as ints in units
+    of 1/1024 (dm_sgm_refine's), and paths 4 or 8 (8 in the first form)."""
+    if not isinstance(sgm, (tuple, list)) or len(sgm) not in (4, 5):
+        raise ValueError('sgm must be (radius, search, p1, p2), (radius, search, p1, p2, paths) or None')
+    paths = sgm[4] if len(sgm) == 5 else 8
+    radius = _int_in(sgm[0], 1, 7, 'sgm radius must be an int in [1, 7] (got %r)')
+    search = _int_in(sgm[1], 1, 3, 'sgm search must be an int in [1, 3] (got %r)')
+    p1 = _real_in(sgm[2], 0.0, 16.0, 'sgm p1 must be a real in [0, 16] (got %r)')
+    p2 = _real_in(sgm[3], 0.0, 16.0, 'sgm p2 must be a real in [0, 16] (got %r)')
+    if p1 > p2:
+        raise ValueError('sgm penalties must satisfy p1 <= p2 (got %r, %r)' % (sgm[2], sgm[3]))
+    if isinstance(paths, bool) or not isinstance(paths, (int, np.integer)) or int(paths) not in (4, 8):
+        raise ValueError('sgm paths must be 4 or 8 (got %r)' % (paths,))
+    return radius, search, int(np.rint(p1 * 1024.0)), int(np.rint(p2 * 1024.0)), int(paths)
+
+
+def sgm_refine(img1, img2, d_row, d_col, radius, search, p1, p2, paths=8, offset=0, subpix=True, mask=None,
+               out=None, return_score=False, return_shift=False, stream=None):
+    """Semi-global re-matching of a disparity map (dm_sgm_refine, include/dmstereo_sgm.h).  Images,
+    planes, ``offset`` and ``radius`` as in photo_score.  Every cell snaps to the nearest integer
+    position and has the (2 search + 1)^2 integer neighbours of it as labels, search in [1, 3]; the
+    cost of a label is 1 - photo_score's correlation there in units of 1/1024, and along ``paths``
+    (4 or 8) scan directions a step of one pixel between the displacements of neighbouring cells
+    costs ``p1``, a larger one ``p2`` (reals in score units, 0 <= p1 <= p2 <= 16).  A cell moves to
+    the label with the smallest sum of path costs (ties: the nearest, then the smaller ay, then the
+    smaller ax); with ``subpix`` a parabola through the sums of the winner's neighbours refines each
+    axis by at most half a pixel.  A cell whose own label wins, a cell that is not finite or that
+    has no scored label keeps its bits.  ``mask``: a uint8 or bool tensor [H][W] on the planes'
+    device; the cells where it is 0 are anchors: they keep their bits and hold their neighbours to
+    their own displacement.  ``out``: a pair of contiguous float64 tensors [H][W] for the two planes
+    (``out=(d_row, d_col)`` works in place when they are contiguous), else new tensors.
+    -> (d_row', d_col'); then, when asked for, the float64 score of the label kept (NaN for a dead
+    cell, an anchor and a cell without a scored label) and the int8 shift [2][H][W] (ay, ax) are
+    appended."""
+    dev = _planes_device(d_row, d_col)
+    radius, search, q1, q2, paths = sgm_params((radius, search, p1, p2, paths))
+    oy, ox = _offset(offset)
+    if mask is not None:
+        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
+                mask.shape == d_row.shape):
+            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
+    if out is not None:
+        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
+                o.shape == d_row.shape and o.is_contiguous() for o in out)):
+            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
+    H, W = d_row.shape
+    with _on(stream):
+        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
+        if a.shape != b.shape:
+            raise ValueError('img1 and img2 must have the same shape')
+        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
+                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
+        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
+        shift = torch.empty((2, H, W), dtype=torch.int8, device=dev) if return_shift else None
+        if H and W:
+            if not a.numel():
+                raise ValueError('empty image')
+            lib = L.load()
+            work = _workspace(lib.dm_sgm_bytes(H, W, search, paths), dev,
+                              'sgm_refine does not take %d x %d cells' % (H, W))
+            m = None if mask is None else mask.to(torch.uint8).contiguous()
+            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernels allow)
+            L.check(lib.dm_sgm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
+                                      L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                      radius, search, paths, q1, q2, L.DM_SGM_SUBPIX if subpix else 0, L.ptr(m),
+                                      L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
+                                      L.stream_handle()), 'dm_sgm_refine')
+    return (o_row, o_col) + ((score,) if return_score else ()) + ((shift,) if return_shift else ())
+
+
+def sgm_stage(img1, img2, d_map, modes, sgm, offset, holes=None):
+    """The ``sgm=`` stage of the chain on the stitched d_map [len(modes)][H][W], in place, after the
+    fill and before the refine stage.  ``sgm``: sgm_params' tuple (the penalties in units of
+    1/1024).  ``holes``: the fill's uint8 mask [len(modes)][H][W] -- only the cells that were filled
+    in the row or in the column plane are matched again, every other cell is an anchor
+    (sgm_where='filled') -- or None: every cell.  -> (d_map, score, int8 shift [2][H][W])."""
+    ir, ic = refine_planes(modes)
+    mask = None if holes is None else (holes[ir] | holes[ic])
+    d_row, d_col, score, shift = sgm_refine(img1, img2, d_map[ir], d_map[ic], sgm[0], sgm[1], sgm[2] / 1024.0,
+                                            sgm[3] / 1024.0, paths=sgm[4], offset=offset, mask=mask,
+                                            out=(d_map[ir], d_map[ic]), return_score=True, return_shift=True)
+    return d_map, score, shift
+
+
 # ---- disparity priors (csrc/dm_prior.hip; include/dmstereo.h has the definitions) ----------------
 def downsample2(img, device=None, stream=None):
     """The half-resolution image (dm_downsample2): a 2-D uint8 image, a numpy array or a tensor

@@ -45,7 +45,9 @@ class ImageCutSolver():
         prior=None,
         coarse=None,
         lsm=None,
-        lsm_where='all'
+        lsm_where='all',
+        sgm=None,
+        sgm_where='all'
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -110,15 +112,24 @@ class ImageCutSolver():
         #       and keeps it if the photo-consistency score rises.  lsm_where: 'all' or 'filled' (needs
         #       fill=).  The modes as for refine.  lsm_score_map is the score of the position kept (NaN: not
         #       scored), lsm_status_map the int8 status [H][W] (iters: accepted, 0: skipped, < 0: kept)
+        #   sgm: (radius, search, p1, p2) or (radius, search, p1, p2, paths) of the semi-global re-matching after
+        #       the fill and before the refine stage: the cells snap to integer positions and are matched again
+        #       together, the (2 search + 1)^2 candidates' costs and a smoothness term (p1 for a step of one pixel
+        #       between neighbouring cells, p2 for more, in score units) minimised along 4 or 8 scan directions.
+        #       sgm_where: 'all' or 'filled' (needs fill=; every other cell is then a fixed anchor).  The modes as
+        #       for refine.  sgm_score_map is the score of the position kept (NaN: not matched), sgm_shift_map the
+        #       int8 shift [2][H][W].  Kept as parsed: the penalties in units of 1/1024
         self.chain = chain.Chain(degree_map_mode, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide,
                                  median=median, median_weight=median_weight, photo=photo, refine=refine,
-                                 refine_where=refine_where, lsm=lsm, lsm_where=lsm_where)
+                                 refine_where=refine_where, lsm=lsm, lsm_where=lsm_where, sgm=sgm,
+                                 sgm_where=sgm_where)
         for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
-                     'refine_where', 'lsm', 'lsm_where'):
+                     'refine_where', 'lsm', 'lsm_where', 'sgm', 'sgm_where'):
             setattr(self, name, getattr(self.chain, name))
         self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
         self.refine_score_map = self.refine_shift_map = None
         self.lsm_score_map = self.lsm_status_map = None
+        self.sgm_score_map = self.sgm_shift_map = None
         # Disparity priors (engine.solve_tiles_prior): tile t's crop of img2 is cut at its origin minus
         # the expected disparity, so that a match outside the tile's own window of img2 can be found.
         #   prior: (d2, d1) ints, one expected ('elevation2', 'elevation') for every tile, in the units and
@@ -201,7 +212,7 @@ class ImageCutSolver():
         With self.merge set the stitch is engine.stitch_merge (both directions when
         self.consistency is set) and the spread and the uint8 count of valid candidates follow
         out_map / the error.  The stitched d_map then runs through self.chain (chain.py: the stages
-        that self.fill, self.speckle, self.smooth, self.median, self.photo, self.refine and self.lsm switch on,
+        that self.fill, self.speckle, self.smooth, self.median, self.photo, self.sgm, self.refine and self.lsm switch on,
         against self.img1 / self.img2 with e = exclusive_pix), which appends the tensors of its
         stages: the tuple is the one chain.Chain.layout names."""
         from deepmatching_stereo_matching_amd import shard
@@ -228,6 +239,7 @@ class ImageCutSolver():
                                              median_weight=self.median_weight, photo=self.photo,
                                              refine=self.refine, refine_where=self.refine_where,
                                              lsm=self.lsm, lsm_where=self.lsm_where,
+                                             sgm=self._sgm_keyword(), sgm_where=self.sgm_where,
                                              prior=self.prior, coarse=self.coarse)
         if self.prior is not None or self.coarse is not None:
             maps = self._stitch_prior(args, n, origins)
@@ -246,6 +258,12 @@ class ImageCutSolver():
             match = engine.solve_tiles(*args)
             maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
         return self.chain.run(maps, self.img1, self.img2, self.exclusive_pix, self.consistency, self.merge)
+
+    def _sgm_keyword(self):
+        """self.sgm (parsed: the penalties in units of 1/1024) as the keyword it was given as."""
+        if self.sgm is None:
+            return None
+        return (self.sgm[0], self.sgm[1], self.sgm[2] / 1024.0, self.sgm[3] / 1024.0, self.sgm[4])
 
     def _stitch_prior(self, args, n, origins):
         """The stitched maps of a solve with priors (self.prior or self.coarse) -> the head of the chain's
@@ -286,6 +304,7 @@ class ImageCutSolver():
              'coverage_map': ('count', False),         # their number
              'speckle_map': ('speckles', True),        # the cells the speckle filter removed (before any fill)
              'hole_map': ('holes', True),              # d_map is dense; the cells that were filled
+             'sgm_score_map': ('sgm_score', False), 'sgm_shift_map': ('sgm_shift', False),
              'refine_score_map': ('refine_score', False), 'refine_shift_map': ('refine_shift', False),
              'lsm_score_map': ('lsm_score', False), 'lsm_status_map': ('lsm_status', False),
              'photo_reject_map': ('rejected', True),   # the cells scoring below min_score (before any fill)

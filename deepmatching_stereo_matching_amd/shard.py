@@ -386,7 +386,8 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
                         smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
                         medianer=None, photo=None, photoer=None, refine=None, refine_where='filled',
-                        refiner=None, prior=None, coarse=None, lsm=None, lsm_where='all', lsmer=None):
+                        refiner=None, prior=None, coarse=None, lsm=None, lsm_where='all', lsmer=None,
+                        sgm=None, sgm_where='all', sgmer=None):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -449,6 +450,13 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     max_move, mask or None) -> (d_row, d_col, score, int8 status [H][W])``).  ``lsm_where``: 'all' or
     'filled' (needs ``fill``).  The float64 score [H][W] and the status come immediately after the
     refine tensors.  None: nothing changes.
+    ``sgm``: (radius, search, p1, p2) or (radius, search, p1, p2, paths), the modes as for ``refine``;
+    rank 0 then matches the cells again together after the fill and before the refine stage
+    (engine.sgm_refine with the offset e, or ``sgmer(img1, img2, d_row, d_col, radius, search, e, p1,
+    p2, paths, mask or None) -> (d_row, d_col, score, int8 shift [2][H][W])`` with the penalties as
+    ints in units of 1/1024).  ``sgm_where``: 'all' or 'filled' (needs ``fill``; every other cell is
+    then a fixed anchor).  The float64 score [H][W] and the shift come immediately before the refine
+    tensors.  None: nothing changes.
     The stages after the stitch, their order and the layout of the tuple are chain.py's (its module
     docstring states the order once); a hook replaces the device stage of its name there.
     ``prior``, ``coarse``: ImageCutSolver's disparity priors; not None raises ValueError -- the bands
@@ -460,7 +468,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
         raise ValueError("result must be 'all' or 'root'")
     post = chain.Chain(modes, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide, median=median,
                        median_weight=median_weight, photo=photo, refine=refine, refine_where=refine_where,
-                       lsm=lsm, lsm_where=lsm_where)
+                       lsm=lsm, lsm_where=lsm_where, sgm=sgm, sgm_where=sgm_where)
     pair = img1, img2      # what the stages read (consistency stacks the pair below)
     if merge is not None:
         engine.merge_rule(merge)
@@ -489,7 +497,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
         maps = post.run(maps, pair[0], pair[1], (window_size - 1) // 2, consistency, merge, filler=filler,
                         speckler=speckler, smoother=smoother, medianer=medianer, photoer=photoer, refiner=refiner,
-                        lsmer=lsmer)
+                        lsmer=lsmer, sgmer=sgmer)
     if not _group() or world()[1] == 1:
         return maps
     H = stride[0] * (n[0] - 1) + image_size[0]

@@ -75,6 +75,51 @@ def subpixel_pair(h, w, seed, ky, kx, up=4):
     return img1, img2
 
 
+def _noisy(img, rng, noise):
+    """img plus one draw of Gaussian noise of its shape, rounded and clipped to uint8."""
+    return np.clip(np.rint(img.astype(np.float64) + rng.normal(0.0, noise, img.shape)), 0, 255).astype(np.uint8)
+
+
+def weak_pair(h, w, seed, block, contrast=1.0 / 16, noise=6.0, dx=2):
+    """Return (img1, img2), uint8 (h, w): stereo_pair's texture shifted by dx columns (the true d_map
+    is 0 in 'elevation2' and dx in 'elevation'), with a weakly textured region under sensor noise.
+    ``block`` = (y0, y1, x0, x1): in the rows y0 .. y1-1 and columns x0 .. x1-1 of img1 -- and so dx
+    columns to the left of them in img2 -- the texture's deviation from the mean of the whole
+    texture is multiplied by ``contrast`` before it is rounded.  Then Gaussian noise of sigma
+    ``noise`` is added to both images, rounded and clipped.  The random draws, in this order:
+    texture(h + 8, w + 8 + dx, seed) with its own generator; then from default_rng([seed, 1]) one
+    normal draw of shape (h, w) for img1, then one for img2."""
+    y0, y1, x0, x1 = block
+    tex = texture(h + 8, w + 8 + dx, seed).astype(np.float64)
+    mean = tex.mean()
+    tex[4 + y0:4 + y1, 4 + x0:4 + x1] = mean + (tex[4 + y0:4 + y1, 4 + x0:4 + x1] - mean) * contrast
+    tex = np.rint(tex)
+    rng = np.random.default_rng([seed, 1])
+    img1 = _noisy(tex[4:4 + h, 4:4 + w], rng, noise)
+    img2 = _noisy(tex[4:4 + h, 4 + dx:4 + dx + w], rng, noise)
+    return img1, img2
+
+
+def step_pair(h, w, seed, xc, d_left=1, d_right=4, noise=6.0):
+    """Return (img1, img2), uint8 (h, w), with a disparity step at column xc: img2's column x' shows
+    the texture of img1's column x' + d_left for x' < xc and of column x' + d_right for x' >= xc,
+    d_right > d_left.  So img1's columns x < xc + d_left have the disparity d_left and its columns
+    x >= xc + d_right the disparity d_right ('elevation'; 'elevation2' is 0); the columns between
+    them are seen nowhere in img2 (the step's occlusion).  Then Gaussian noise of sigma ``noise`` is
+    added to both images, rounded and clipped.  The random draws, in this order:
+    texture(h + 8, w + 8 + d_right, seed) with its own generator; then from default_rng([seed, 2])
+    one normal draw of shape (h, w) for img1, then one for img2."""
+    if not d_right > d_left >= 0:
+        raise ValueError('step_pair needs 0 <= d_left < d_right')
+    tex = texture(h + 8, w + 8 + d_right, seed)
+    xx = np.arange(w)
+    src = np.where(xx < xc, xx + d_left, xx + d_right)
+    rng = np.random.default_rng([seed, 2])
+    img1 = _noisy(tex[4:4 + h, 4:4 + w], rng, noise)
+    img2 = _noisy(tex[4:4 + h, 4 + src], rng, noise)
+    return img1, img2
+
+
 CONTENT_KINDS = ('binary', 'identical', 'dark', 'bright', 'dark_bright', 'low4', 'high4',
                  'checker', 'stripes', 'edge', 'const')
 

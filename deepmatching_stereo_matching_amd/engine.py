@@ -1066,8 +1066,9 @@ def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps
             lib = L.load()
             work = _workspace(lib.dm_photo_bytes(M, H, W), dev,
                               'photo_score does not take %d maps of %d x %d cells' % (M, H, W))
+            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
             L.check(lib.dm_photo_score(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                       L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                       L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
                                        radius, L.DM_PHOTO_REJECT if min_score is not None else 0,
                                        min_score if min_score is not None else 0.0,
                                        L.ptr(out) if min_score is not None else L.ptr(None), M, L.ptr(score),
@@ -1170,8 +1171,9 @@ def photo_refine(img1, img2, d_row, d_col, radius, search, offset=0, min_gain=0.
                               (H, W, a.shape[0], a.shape[1]))
             m = None if mask is None else mask.to(torch.uint8).contiguous()
             # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
+            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
             L.check(lib.dm_photo_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                        L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                        L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
                                         radius, search, min_gain, L.DM_REFINE_SUBPIX if subpix else 0, L.ptr(m),
                                         L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
                                         L.stream_handle()), 'dm_photo_refine')
@@ -1252,8 +1254,9 @@ def lsm_refine(img1, img2, d_row, d_col, radius, iters, offset=0, max_move=1.0, 
                               (H, W, a.shape[0], a.shape[1]))
             m = None if mask is None else mask.to(torch.uint8).contiguous()
             # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
+            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
             L.check(lib.dm_lsm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                      L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                      L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
                                       radius, iters, max_move, 0, L.ptr(m), L.ptr(o_row), L.ptr(o_col),
                                       L.ptr(score), L.ptr(status), L.ptr(work), L.stream_handle()), 'dm_lsm_refine')
     return (o_row, o_col) + ((score,) if return_score else ()) + ((status,) if return_status else ())
@@ -1340,8 +1343,9 @@ def sgm_refine(img1, img2, d_row, d_col, radius, search, p1, p2, paths=8, offset
                               'sgm_refine does not take %d x %d cells' % (H, W))
             m = None if mask is None else mask.to(torch.uint8).contiguous()
             # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernels allow)
+            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
             L.check(lib.dm_sgm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                      L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), H, W, int(oy), int(ox),
+                                      L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
                                       radius, search, paths, q1, q2, L.DM_SGM_SUBPIX if subpix else 0, L.ptr(m),
                                       L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
                                       L.stream_handle()), 'dm_sgm_refine')
@@ -1446,7 +1450,8 @@ def tile_prior(d_row, d_col, origins, h0, w0, e, scale=2, stream=None):
         T = len(o)
         q = torch.empty((T, 2), dtype=torch.int32, device=dev)
         valid = torch.empty((T,), dtype=torch.uint8, device=dev)
-        L.check(L.load().dm_tile_prior(L.ptr(d_row.contiguous()), L.ptr(d_col.contiguous()), d_row.shape[0],
+        rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
+        L.check(L.load().dm_tile_prior(L.ptr(rows), L.ptr(cols), d_row.shape[0],
                                        d_row.shape[1], L.ptr(o), T, h0, w0, e, int(scale), L.ptr(q), L.ptr(valid),
                                        L.stream_handle()), 'dm_tile_prior')
     return q, valid

@@ -93,7 +93,18 @@ class DevicePyramid:
       1  dm_corr_level12 writes levels 1 and 2 in one pass (no level-1 re-read);
       2  dm_corr_level12 writes level 2 only: level 1 stays on chip (levels[1] is None
          until ``level(1)`` asks for it) and matching evaluates it on demand.
-    levels[l] for the others are float64 [T][Pl][Pl] tensors."""
+    levels[l] for the others are float64 [T][Pl][Pl] tensors.
+
+    Streams (DESIGN.md section 5c has the ledger of every hand-off).  ``stream``: the stream
+    every call of this pyramid launches on -- the pair stream; None: the stream that is
+    current at each call.  Buffers are allocated from the pair stream's pool whether or not
+    it is torch's current stream, so ``DevicePyramid(batch, stream=side)`` may be used while
+    another stream is current.  A call made on another pair stream than the call before it (a
+    pyramid without a stream of its own, called under two current streams) first waits for
+    that earlier stream, and every buffer the pyramid owns is recorded on each stream that
+    touches it.  What a call returns (``match``'s map, ``level(k)``, ``volume()``) belongs to
+    the pair stream of that call: a caller reading it elsewhere orders and records that read
+    itself, as for any torch tensor."""
 
     def __init__(self, batch, stream=None, build=True, fuse_level2=None, stats_stream=None):
         """stats_stream: optional stream the per-patch stats and window operands
@@ -109,15 +120,13 @@ class DevicePyramid:
         self.stream = stream
         self._stats_stream = stats_stream
         self._stats_ready = None
+        self._home = None      # the pair stream of the latest call: ordered after all work so far
         nbytes = self.lib.dm_stats_bytes(batch.ref())
-        if stats_stream is None:
+        # from the stats stream's pool, or the pair stream's; every other stream that touches it
+        # is recorded where it does (_pair, build), so the caching allocator reuses it only
+        # after their work on it has finished
+        with _on(stats_stream if stats_stream is not None else stream):
             self.stats = torch.empty(nbytes, dtype=torch.uint8, device=batch.device)
-        else:
-            # from the stats stream's pool; every other stream that touches it is recorded, so
-            # the caching allocator reuses it only after their work on it has finished
-            with torch.cuda.stream(stats_stream):
-                self.stats = torch.empty(nbytes, dtype=torch.uint8, device=batch.device)
-            self.stats.record_stream(stream if stream is not None else torch.cuda.current_stream())
         if fuse_level2 is None:
             fuse_level2 = int(os.environ.get('DM_FUSE_L2', str(FUSE_DEFAULT)))
         self.fuse_level2 = int(fuse_level2)
@@ -130,6 +139,20 @@ class DevicePyramid:
 
     def _s(self):
         return L.stream_handle(self.stream)
+
+    def _pair(self):
+        """The pair stream of this call (``stream``, or the current one), ordered after the
+        pair stream of the call before it when that was another, with the pyramid's buffers
+        recorded on it (a no-op on the stream whose pool a buffer came from)."""
+        st = self.stream if self.stream is not None else torch.cuda.current_stream()
+        if self._home is None or st != self._home:
+            if self._home is not None:
+                st.wait_stream(self._home)
+            for t in [self.stats, self._volume] + self.levels:
+                if t is not None:
+                    t.record_stream(st)
+            self._home = st
+        return st
 
     @property
     def nlev(self):
@@ -146,13 +169,14 @@ class DevicePyramid:
         return self._plan[1]
 
     def compute_stats(self):
+        st = self._pair()
         if not self._have_stats:
             ss = self._stats_stream
             if ss is not None:
                 # forward order: the images / origins may have been written on this pyramid's
                 # own stream (a conversion, a non-blocking upload); the stats read them
                 ready = torch.cuda.Event()
-                ready.record(self.stream if self.stream is not None else torch.cuda.current_stream())
+                ready.record(st)
                 ss.wait_event(ready)
             L.check(self.lib.dm_corr_stats(self.b.ref(), L.ptr(self.stats),
                                            L.stream_handle(ss) if ss is not None else self._s()),
@@ -160,8 +184,7 @@ class DevicePyramid:
             if ss is not None:
                 self._stats_ready = torch.cuda.Event()
                 self._stats_ready.record(ss)
-                (self.stream if self.stream is not None else torch.cuda.current_stream()).wait_event(
-                    self._stats_ready)
+                st.wait_event(self._stats_ready)
             self._have_stats = True
         return self
 
@@ -172,7 +195,9 @@ class DevicePyramid:
 
     def _level1(self, stream=None, l1=None):
         if l1 is None:
-            l1 = self._empty_level(1)
+            self._pair()
+            with _on(self.stream):
+                l1 = self._empty_level(1)
         sh = L.stream_handle(stream) if stream is not None else self._s()
         L.check(self.lib.dm_corr_level1(self.b.ref(), L.ptr(self.stats), L.ptr(l1), sh),
                 'dm_corr_level1')
@@ -195,10 +220,10 @@ class DevicePyramid:
         pair stream.  Building more levels later extends the pyramid."""
         b, lib = self.b, self.lib
         self.compute_stats()
+        st = self._pair()
         top = self.nlev if nlev is None else max(1, min(int(nlev), self.nlev))
         if top > 1 and len(self.levels) == 1:
             fused = False
-            st = self.stream if self.stream is not None else torch.cuda.current_stream()
             ls = st
             if level_stream is not None and level_stream != st:
                 ls = level_stream
@@ -248,7 +273,8 @@ class DevicePyramid:
         while len(self.levels) < top:
             k = len(self.levels)               # build level k from level k - 1
             h, w = b.h0 >> (k - 1), b.w0 >> (k - 1)
-            nxt = self._empty_level(k)
+            with _on(self.stream):
+                nxt = self._empty_level(k)
             L.check(lib.dm_aggregate(L.ptr(self.levels[k - 1]), b.T, h, w, 1, L.ptr(nxt),
                                      self._s()), 'dm_aggregate')
             self.levels.append(nxt)
@@ -273,16 +299,18 @@ class DevicePyramid:
         """Level-0 min-max volume (co_map before rectification), float32 [T][P][P]."""
         if self._volume is None:
             b = self.b
-            self._volume = self._volume_into(torch.empty((b.T, b.P, b.P), dtype=torch.float32,
-                                                         device=b.device), False)
+            with _on(self.stream):
+                v = torch.empty((b.T, b.P, b.P), dtype=torch.float32, device=b.device)
+            self._volume = self._volume_into(v, False)
         return self._volume
 
     def volume_f16(self):
         """The level-0 min-max volume as binary16 (dm_corr_volume_f16, BASELINE config C5's
         fp16 correlation): float16 [T][P][P], each value np.float16 of volume()'s."""
         b = self.b
-        return self._volume_into(torch.empty((b.T, b.P, b.P), dtype=torch.float16, device=b.device),
-                                 True)
+        with _on(self.stream):
+            v = torch.empty((b.T, b.P, b.P), dtype=torch.float16, device=b.device)
+        return self._volume_into(v, True)
 
     def materialized_levels(self, l0_dtype='f32'):
         """co_map_list built the reference's way (misc/Correlation_map.py:132-156): level 0
@@ -293,7 +321,9 @@ class DevicePyramid:
         Needs T * P^2 * (8 + 2|4) bytes of HBM."""
         b, lib = self.b, self.lib
         v = self.volume_f16() if l0_dtype == 'f16' else self.volume()
-        l0 = torch.empty(v.shape, dtype=torch.float64, device=v.device)
+        self._pair()
+        with _on(self.stream):
+            l0 = torch.empty(v.shape, dtype=torch.float64, device=v.device)
         fn = lib.dm_rectify_f16 if l0_dtype == 'f16' else lib.dm_rectify
         L.check(fn(L.ptr(v), v.numel(), L.ptr(l0), self._s()), 'dm_rectify')
         if l0_dtype == 'f16':
@@ -301,7 +331,8 @@ class DevicePyramid:
         levels, h, w = [l0], b.h0, b.w0
         for _ in range(1, self.nlev):
             P2 = (h // 2) * (w // 2)
-            nxt = torch.empty((b.T, P2, P2), dtype=torch.float64, device=b.device)
+            with _on(self.stream):
+                nxt = torch.empty((b.T, P2, P2), dtype=torch.float64, device=b.device)
             L.check(lib.dm_aggregate(L.ptr(levels[-1]), b.T, h, w, 1, L.ptr(nxt), self._s()),
                     'dm_aggregate')
             levels.append(nxt)
@@ -321,7 +352,9 @@ class DevicePyramid:
                 self.levels[k] = self._level1()
             return self.levels[k]
         v = self.volume()
-        out = torch.empty(v.shape, dtype=torch.float64, device=v.device)
+        self._pair()
+        with _on(self.stream):
+            out = torch.empty(v.shape, dtype=torch.float64, device=v.device)
         L.check(self.lib.dm_rectify(L.ptr(v), v.numel(), L.ptr(out), self._s()), 'dm_rectify')
         return out
 
@@ -344,8 +377,10 @@ class DevicePyramid:
                 self.level(k)
             if n == 2 and self.levels[1] is None:   # the top level must be stored
                 self.level(1)
-        out = torch.empty((b.T, 3, b.h0, b.w0), dtype=torch.float64, device=b.device)
-        scratch = torch.empty_like(out)
+        self._pair()
+        with _on(self.stream):
+            out = torch.empty((b.T, 3, b.h0, b.w0), dtype=torch.float64, device=b.device)
+            scratch = torch.empty_like(out)
         if levels is not None:
             ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in levels[:n]])
         else:
@@ -404,7 +439,12 @@ def subpix_map_tiles(pyr, match, stream=None):
     """subpix_map with level 0 on demand (dm_subpix_map_tiles): the five level-0 values an entry
     reads are recomputed from the pyramid's images and statistics, so co_map_list[0] is never
     materialised.  `match`: contiguous float64 device tensor [T][3][hm][wm] (or [3][hm][wm]
-    when the batch holds one tile), refined in place."""
+    when the batch holds one tile), refined in place.  ``stream``: the stream the refinement runs
+    on (None: the pyramid's pair stream); it waits for the pyramid's pair stream when it is another
+    one, and the stats workspace is recorded on it.  Like every call of a pyramid this one goes
+    through DevicePyramid._pair, ``stream`` given or not: a pyramid without a stream of its own,
+    called here under another current stream than at its call before, makes that current stream
+    wait for the earlier one (a ``wait_stream`` enqueued on the caller's current stream)."""
     if not isinstance(match, torch.Tensor) or not match.is_cuda:
         raise ValueError('match must be a device (cuda) tensor: the kernel refines it in place')
     m = match if match.dim() == 4 else match[None]
@@ -413,8 +453,10 @@ def subpix_map_tiles(pyr, match, stream=None):
         raise ValueError('match must be a contiguous float64 [T][3][h][w] tensor (T = %d)' % b.T)
     if not pyr._have_minmax:   # the per-patch min / max a level kernel or volume leaves in the stats
         pyr.build(nlev=2)
-    if stream is not None and pyr.stream is not None and stream != pyr.stream:
-        stream.wait_stream(pyr.stream)   # the stats the pyramid's stream wrote
+    home = pyr._pair()
+    if stream is not None and stream != home:
+        stream.wait_stream(home)           # the stats the pyramid's pair stream wrote, whether
+        pyr.stats.record_stream(stream)    # it has a stream of its own or ran on the current one
     _, _, hm, wm = m.shape
     L.check(pyr.lib.dm_subpix_map_tiles(b.ref(), L.ptr(pyr.stats), hm, wm, L.ptr(m),
                                         L.stream_handle(stream) if stream is not None else pyr._s()),

@@ -131,9 +131,19 @@ def _run_levels(kind, m, s0, s1, e, fn):
     return len(off) - 1
 
 
+# the forward sweep's exact level count where the case is there for it (a row of k updates is a
+# chain of k levels; the backward sweep alternates between two rows, so its row is one level)
+LOOP_LEVELS = {(9, 10, 6, 6, 2): 1,                               # one update
+               (9, 9, 4, 5, 1): 2, (9, 9, 4, 6, 1): 3, (8, 7, 3, 2, 0): 2, (10, 11, 8, 6, 2): 3,
+               (10, 14, 4, 12, 1): 9,                             # one row of updates
+               (14, 10, 12, 4, 1): 9}                             # one column
+
+
 @pytest.mark.parametrize('h,w,s0,s1,e', [(24, 31, 24, 31, 1), (20, 22, 18, 17, 3), (13, 15, 12, 14, 0),
-                                         (40, 9, 40, 9, 1), (7, 7, 7, 7, 3)])
+                                         (40, 9, 40, 9, 1), (7, 7, 7, 7, 3),
+                                         (19, 23, 15, 18, 1)] + sorted(LOOP_LEVELS))   # sub-sized in both axes
 def test_schedule_optimize_loop(h, w, s0, s1, e):
+    nl = LOOP_LEVELS.get((h, w, s0, s1, e))
     rng = np.random.default_rng(h * 100 + w)
     img = O.image_threshold(rng.uniform(-2, 12, (h, w)))
     coef = rng.uniform(0, 2, (h, w))
@@ -142,9 +152,17 @@ def test_schedule_optimize_loop(h, w, s0, s1, e):
     nl_f = _run_levels(0, m, s0, s1, e, lambda mm, r, c: _upd4(mm, coef, 0.008, r, c))
     nl_b = _run_levels(1, m, s0, s1, e, lambda mm, r, c: _upd4(mm, coef, 0.008, r, c))
     assert same(m, ref)
+    assert nl is None or nl_f == nl
     n = max(0, s0 - 2 * e - 1) * max(0, s1 - 2 * e - 1)
-    if n:  # the schedule is parallel: far fewer levels than updates
+    # the schedule is parallel: far fewer levels than updates (a single column of updates is a
+    # dependency chain in both directions: as many levels as updates)
+    if n and s1 - 2 * e - 1 > 1:
         assert nl_f <= (s0 - 2 * e - 1) + (s1 - 2 * e - 1) and nl_b < n or n < 4
+
+
+# exact level counts of the fixtures that are there for them; a sweep narrower than its map
+BILAT_LEVELS = {'opt_bilat_8x9_e2_one.npz': 1, 'opt_bilat_8x9_e1_two.npz': 2, 'opt_bilat_9x8_e1_three.npz': 3,
+                'opt_bilat_9x12_e1_row.npz': 8, 'opt_bilat_12x9_e1_col.npz': 8}
 
 
 @pytest.mark.parametrize('path', gold('bilat'), ids=os.path.basename)
@@ -158,8 +176,22 @@ def test_schedule_bilateral(path):
         a = -(c0 - (cp + cm) / 2.0)
         K = (cp - cm) / 2.0 / (-2.0 * c0 + cp + cm)
         m = z['img'].copy()
-        _run_levels(2, m, size[0], size[1], e, lambda mm, r, c: _updb(mm, z['color'], z['gauss'], a, K, e, r, c))
+        nl = _run_levels(2, m, size[0], size[1], e,
+                         lambda mm, r, c: _updb(mm, z['color'], z['gauss'], a, K, e, r, c))
         assert same(m, z['out_' + key]), key
+        assert nl == BILAT_LEVELS.get(os.path.basename(path), nl)
+
+
+def test_schedule_bilateral_geometries():
+    """the fixtures test_schedule_bilateral runs on include sweeps narrower than the map in both
+    axes and schedules of exactly 1, 2 and 3 levels"""
+    names = {os.path.basename(p) for p in gold('bilat')}
+    assert set(BILAT_LEVELS) <= names
+    sub = set()
+    for z in map(np.load, gold('bilat')):
+        if z['size'][0] < z['img'].shape[0] and z['size'][1] < z['img'].shape[1]:
+            sub.add(int(z['exclusion']))
+    assert sub >= {1, 2, 3}
 
 
 def test_schedule_rejects_bad_shapes():

@@ -31,6 +31,8 @@ replaced by a host function (the hooks of solve_image_sharded); the calls are th
 the stage functions below.
 """
 
+from collections import namedtuple
+from functools import partial
 from types import SimpleNamespace
 
 import numpy as np
@@ -79,47 +81,34 @@ def _fill(c, v, r):
         v['d_map'], v['holes'] = engine.fill_holes(v['d_map'], c.fill, out=v['d_map'], return_holes=True)
 
 
-def _sgm(c, v, r):
-    if c.sgm is None:
+# The stages that match the two elevation planes again, in the order they run in.  key: the keyword (its
+# `<key>_where` keyword picks the cells, and the stage adds `<key>_score` [H][W]); hook: the keyword of Chain.run that
+# replaces it; stage: the engine function; aux: the int8 tensor it adds and the dimensions that precede [H][W].
+# Every hook is called as hook(img1, img2, d_row, d_col, p[0], p[1], e, *p[2:], mask) with p the parsed keyword.
+PlaneStage = namedtuple('PlaneStage', 'key hook stage aux lead')
+SGM = PlaneStage('sgm', 'sgmer', 'sgm_stage', 'sgm_shift', (2,))
+REFINE = PlaneStage('refine', 'refiner', 'refine_stage', 'refine_shift', (2,))
+LSM = PlaneStage('lsm', 'lsmer', 'lsm_stage', 'lsm_status', ())
+PLANE_STAGES = (SGM, REFINE, LSM)
+
+
+def _plane(st, c, v, r):
+    p = getattr(c, st.key)
+    if p is None:
         return
     d = v['d_map']
-    holes = v['holes'] if c.sgm_where == 'filled' else None
-    if r.sgmer is not None:
+    holes = v['holes'] if getattr(c, st.key + '_where') == 'filled' else None
+    hook = getattr(r, st.hook)
+    if hook is not None:
         row, col = engine.refine_planes(c.modes)
         mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
-        d[row], d[col], v['sgm_score'], v['sgm_shift'] = r.sgmer(
-            r.img1, r.img2, d[row], d[col], c.sgm[0], c.sgm[1], r.e, c.sgm[2], c.sgm[3], c.sgm[4], mask)
+        d[row], d[col], v[st.key + '_score'], v[st.aux] = hook(r.img1, r.img2, d[row], d[col], p[0], p[1], r.e, *p[2:],
+                                                               mask)
     else:
-        v['d_map'], v['sgm_score'], v['sgm_shift'] = engine.sgm_stage(r.img1, r.img2, d, c.modes, c.sgm, r.e, holes)
+        v['d_map'], v[st.key + '_score'], v[st.aux] = getattr(engine, st.stage)(r.img1, r.img2, d, c.modes, p, r.e, holes)
 
 
-def _refine(c, v, r):
-    if c.refine is None:
-        return
-    d = v['d_map']
-    holes = v['holes'] if c.refine_where == 'filled' else None
-    if r.refiner is not None:
-        row, col = engine.refine_planes(c.modes)
-        mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
-        d[row], d[col], v['refine_score'], v['refine_shift'] = r.refiner(
-            r.img1, r.img2, d[row], d[col], c.refine[0], c.refine[1], r.e, c.refine[2], mask)
-    else:
-        v['d_map'], v['refine_score'], v['refine_shift'] = engine.refine_stage(r.img1, r.img2, d, c.modes, c.refine,
-                                                                              r.e, holes)
-
-
-def _lsm(c, v, r):
-    if c.lsm is None:
-        return
-    d = v['d_map']
-    holes = v['holes'] if c.lsm_where == 'filled' else None
-    if r.lsmer is not None:
-        row, col = engine.refine_planes(c.modes)
-        mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
-        d[row], d[col], v['lsm_score'], v['lsm_status'] = r.lsmer(
-            r.img1, r.img2, d[row], d[col], c.lsm[0], c.lsm[1], r.e, c.lsm[2], mask)
-    else:
-        v['d_map'], v['lsm_score'], v['lsm_status'] = engine.lsm_stage(r.img1, r.img2, d, c.modes, c.lsm, r.e, holes)
+_sgm, _refine, _lsm = (partial(_plane, st) for st in PLANE_STAGES)
 
 
 def _smooth(c, v, r):
@@ -170,21 +159,13 @@ class Chain:
         self.photo = engine.photo_params(photo) if photo is not None else None
         if self.photo is not None:
             engine.photo_planes(modes)
-        self.refine = engine.refine_params(refine) if refine is not None else None
-        self.refine_where = refine_where
-        if self.refine is not None:
-            engine.refine_planes(modes)
-            engine.refine_where(refine_where, self.fill)
-        self.lsm = engine.lsm_params(lsm) if lsm is not None else None
-        self.lsm_where = lsm_where
-        if self.lsm is not None:
-            engine.refine_planes(modes)
-            engine.refine_where(lsm_where, self.fill, 'lsm_where')
-        self.sgm = engine.sgm_params(sgm) if sgm is not None else None
-        self.sgm_where = sgm_where
-        if self.sgm is not None:
-            engine.refine_planes(modes)
-            engine.refine_where(sgm_where, self.fill, 'sgm_where')
+        for st, p, where in ((REFINE, refine, refine_where), (LSM, lsm, lsm_where), (SGM, sgm, sgm_where)):
+            p = getattr(engine, st.key + '_params')(p) if p is not None else None
+            setattr(self, st.key, p)
+            setattr(self, st.key + '_where', where)
+            if p is not None:
+                engine.refine_planes(modes)
+                engine.refine_where(where, self.fill, st.key + '_where')
 
     def layout(self, H, W, consistency, merge):
         """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
@@ -200,12 +181,9 @@ class Chain:
             lay.append(('speckles', (M, H, W), u8))
         if self.fill is not None:
             lay.append(('holes', (M, H, W), u8))
-        if self.sgm is not None:
-            lay += [('sgm_score', (H, W), f64), ('sgm_shift', (2, H, W), torch.int8)]
-        if self.refine is not None:
-            lay += [('refine_score', (H, W), f64), ('refine_shift', (2, H, W), torch.int8)]
-        if self.lsm is not None:
-            lay += [('lsm_score', (H, W), f64), ('lsm_status', (H, W), torch.int8)]
+        for st in PLANE_STAGES:
+            if getattr(self, st.key) is not None:
+                lay += [(st.key + '_score', (H, W), f64), (st.aux, st.lead + (H, W), torch.int8)]
         if self.photo is not None:
             if self.photo[1] is not None:
                 lay.append(('rejected', (H, W), u8))

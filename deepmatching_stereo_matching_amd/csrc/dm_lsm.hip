@@ -195,11 +195,10 @@ __device__ __forceinline__ bool lsm_inside(double py, double px, int Hi, int Wi,
 // (it cannot: the test repeats lsm_inside on the converted value, before anything is read)
 __device__ __forceinline__ bool lsm_split(double py, double px, int Hi, int Wi, int r, int &iy, int &ix, double (&w)[4])
 {
-    const double fly = floor(py), flx = floor(px);
-    iy = (int)fly, ix = (int)flx;
-    const double fy = py - fly, fx = px - flx;
-    const double gy = 1.0 - fy, gx = 1.0 - fx;
-    w[0] = gy * gx, w[1] = gy * fx, w[2] = fy * gx, w[3] = fy * fx;
+    const PhoPos pos = pho_bilin(py, px);
+    iy = pos.iy, ix = pos.ix;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) w[k] = pos.w[k];
     return iy >= r && iy <= Hi - r - 2 && ix >= r && ix <= Wi - r - 2;
 }
 
@@ -211,12 +210,11 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_lsm(const uint8_t *img1, siz
                                                        int r, int iters, double max_move, const uint8_t *mask,
                                                        double *out_row, double *out_col, double *score, int8_t *status)
 {
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
-    if (y >= H || x >= W) return;
+    int y, x;
+    if (!pho_cell(tiles_x, H, W, y, x)) return;
     const size_t c = (size_t)y * W + x;
     const double dr = d_row[c], dc = d_col[c];
-    const double NaN = __longlong_as_double(0x7ff8000000000000LL);
+    const double NaN = dm_nan();
     double o_row = dr, o_col = dc, o_score = NaN;
     int o_status = 0;
     const int cy = y + oy, cx = x + ox;
@@ -292,12 +290,11 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_lsm(const uint8_t *img1, siz
 }
 
 // ---- host side ------------------------------------------------------------------------------
-// false for a shape the entry does not take (dm_photo_bytes' limits, and images of at most 2^30 a side)
+// false for a shape the entry does not take
 static bool lsm_plan(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t iters)
 {
     if (radius < 1 || radius > PHO_RMAX || iters < 1 || iters > LSM_ITMAX) return false;
-    if (Hi < 1 || Wi < 1 || Hi > (1 << 30) || Wi > (1 << 30)) return false;
-    return dm_photo_bytes(1, H, W) != 0;
+    return pho_pair_plan(Hi, Wi, H, W);
 }
 
 extern "C" {
@@ -314,14 +311,7 @@ int dm_lsm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2,
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_out_row || !d_out_col || !d_work)
         return dm_fail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
-    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
-    if (stride1 < Wi || stride2 < Wi)
-        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
-                     (long long)stride2);
-    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
-    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (const int bad = pho_pair_args(stride1, stride2, Hi, Wi, H, W, oy, ox, radius)) return bad;
     if (iters < 1 || iters > LSM_ITMAX) return dm_fail(DM_ERR_ARG, "iters must be in [1, %d] (got %d)", LSM_ITMAX, iters);
     if (!(max_move > 0.0 && max_move <= 2.0)) return dm_fail(DM_ERR_ARG, "max_move must be in (0, 2] (got %g)", max_move);
     if (flags != 0) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
@@ -329,19 +319,14 @@ int dm_lsm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2,
         return dm_fail(DM_ERR_UNSUPPORTED,
                      "lsm refine of %d x %d cells on a %d x %d image (at most 2^31 - 1 cells, 2^30 pixels a side)", H, W,
                      Hi, Wi);
-    const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
+    int tiles_x;
+    const dim3 grid = pho_grid(H, W, &tiles_x);
     hipStream_t st = (hipStream_t)stream;
 #define LSM_GO(ND_)                                                                                             \
     k_lsm<ND_><<<grid, PHO_TX * PHO_TY, 0, st>>>(d_img1, (size_t)stride1, d_img2, (size_t)stride2, Hi, Wi, d_row,  \
                                                  d_col, H, W, tiles_x, oy, ox, radius, iters, max_move, d_mask,   \
                                                  d_out_row, d_out_col, d_score, d_status)
-    switch ((radius + 2) / 2) {
-    case 1: LSM_GO(1); break;
-    case 2: LSM_GO(2); break;
-    case 3: LSM_GO(3); break;
-    default: LSM_GO(4); break;
-    }
+    PHO_SWITCH_ND(radius, LSM_GO)
 #undef LSM_GO
     DM_HIP_TRY(hipGetLastError());
     return DM_OK;

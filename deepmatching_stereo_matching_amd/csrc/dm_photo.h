@@ -1,15 +1,79 @@
-// dm_photo.h -- device helpers shared by dm_photo.hip (dm_photo_score), dm_photo_refine.hip
-// (dm_photo_refine) and dm_lsm.hip (dm_lsm_refine): rows of uint8 pixels read as unaligned dwords,
-// and sums of products as chains of v_dot4_u32_u8.
+// dm_photo.h -- what the four stages that read the image pair share: dm_photo.hip (dm_photo_score),
+// dm_photo_refine.hip (dm_photo_refine), dm_lsm.hip (dm_lsm_refine) and dm_sgm.hip (dm_sgm_refine).
+//
+// Host side, used by all four entries:
+//   pho_pair_args   the argument checks they have in common (image shape, strides, map shape, offset,
+//                   radius), in that order, with their messages
+//   pho_pair_plan   the shapes a plane re-matching entry takes (refine, lsm, sgm)
+//   pho_grid, PHO_SWITCH_ND   the launch grid of one thread per cell and the dispatch on ND = (radius + 2) / 2
+// Device side:
+//   pho_cell        the cell of a thread (k_photo, k_refine, k_lsm, k_sgm_cost, k_sgm_pick)
+//   pho_row, pho_rowz, pho_shift, pho_wmask   rows of uint8 pixels read as unaligned dwords and cut into
+//                   shifted window rows (all four; the 3-byte case of pho_rowz is k_sgm_cost's)
+//   pho_dot, pho_sum   sums of products as chains of v_dot4_u32_u8 (all four)
+//   pho_moments1    sum A and sum A^2 of the img1 window (k_refine, k_sgm_cost)
+//   pho_bilin       a position as its integer corner and bilinear weights (k_photo, k_refine, k_lsm)
+//   pho_numvb, pho_zncc   the float64 tail of dm_photo_score's rule 5 (k_photo, k_refine, k_lsm; pho_zncc
+//                   also k_sgm_cost and k_sgm_pick)
 #ifndef DM_PHOTO_H
 #define DM_PHOTO_H
 
-#include "dm_host.h"      // dm_is_hole; dm_fail and dm_maps_plan for the two entries
+#include "dm_host.h"      // dm_is_hole, dm_nan; dm_fail and dm_maps_plan for the entries
 
 #define PHO_TX 32
 #define PHO_TY 8
 #define PHO_RMAX 7
 #define PHO_OFFMAX (1 << 30)
+
+// ---- host side ------------------------------------------------------------------------------
+// the checks every entry makes on the pair, the map and the window: DM_OK, or the code of the first that fails
+__attribute__((unused)) static int pho_pair_args(int64_t stride1, int64_t stride2, int32_t Hi, int32_t Wi, int32_t H,
+                                                 int32_t W, int32_t oy, int32_t ox, int32_t radius)
+{
+    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
+    if (stride1 < Wi || stride2 < Wi)
+        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
+                     (long long)stride2);
+    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
+    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
+        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
+    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    return DM_OK;
+}
+
+// false for a shape the plane re-matching entries do not take (dm_photo_bytes' limits, and images of at most
+// 2^30 a side)
+__attribute__((unused)) static bool pho_pair_plan(int32_t Hi, int32_t Wi, int32_t H, int32_t W)
+{
+    if (Hi < 1 || Wi < 1 || Hi > (1 << 30) || Wi > (1 << 30)) return false;
+    return dm_photo_bytes(1, H, W) != 0;
+}
+
+// the grid of one thread per cell: tiles_x * tiles_y workgroups of PHO_TX x PHO_TY cells (tiles_x tiles_y < 2^31)
+__attribute__((unused)) static dim3 pho_grid(int32_t H, int32_t W, int *tiles_x)
+{
+    const int tiles_y = (H + PHO_TY - 1) / PHO_TY;
+    *tiles_x = (W + PHO_TX - 1) / PHO_TX;
+    return dim3((unsigned)*tiles_x * (unsigned)tiles_y);
+}
+
+// GO(ND) for the ND = (radius + 2) / 2 dwords of a window row of 2 radius + 1 bytes
+#define PHO_SWITCH_ND(radius, GO) \
+    switch (((radius) + 2) / 2) { \
+    case 1: GO(1); break;         \
+    case 2: GO(2); break;         \
+    case 3: GO(3); break;         \
+    default: GO(4); break;        \
+    }
+
+// ---- device side ----------------------------------------------------------------------------
+// the cell (y, x) of this thread in a pho_grid launch; false outside the map
+__device__ __forceinline__ bool pho_cell(int tiles_x, int H, int W, int &y, int &x)
+{
+    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
+    return y < H && x < W;
+}
 
 __device__ __forceinline__ bool pho_finite(double x) { return !dm_is_hole(x); }
 
@@ -35,11 +99,17 @@ __device__ __forceinline__ void pho_row(const uint8_t *p, int nbytes, uint32_t (
     d[ND - 1] = pho_ld4(p + nbytes - 4) >> (8 * (4 - rem));
 }
 
-// the first nbytes (4 .. 4 NW) bytes at p as NW little-endian dwords, zero from nbytes on.  Reads
-// nothing outside [p, p + nbytes).
-template <int NW>
+// the first nbytes (4 .. 4 NW; with B3 3 .. 4 NW) bytes at p as NW little-endian dwords, zero from nbytes
+// on.  Reads nothing outside [p, p + nbytes).
+template <int NW, bool B3 = false>
 __device__ __forceinline__ void pho_rowz(const uint8_t *p, int nbytes, uint32_t (&d)[NW])
 {
+    if (B3 && nbytes < 4) {
+        d[0] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
+#pragma unroll
+        for (int k = 1; k < NW; ++k) d[k] = 0u;
+        return;
+    }
 #pragma unroll
     for (int k = 0; k < NW; ++k) {
         const int left = nbytes - 4 * k;      // bytes of the row from dword k on
@@ -90,6 +160,39 @@ __device__ __forceinline__ uint32_t pho_sum(const uint32_t (&a)[ND], uint32_t ac
 #pragma unroll
     for (int k = 0; k < ND; ++k) acc = __builtin_amdgcn_udot4(a[k], 0x01010101u, acc, false);
     return acc;
+}
+
+// sum A and sum A^2 of the img1 window whose top-left byte is pa
+template <int ND>
+__device__ __forceinline__ void pho_moments1(const uint8_t *pa, size_t stride1, int D, const uint32_t (&wmask)[ND],
+                                             uint32_t &sa, uint32_t &saa)
+{
+    sa = 0, saa = 0;
+    for (int q = 0; q < D; ++q) {
+        uint32_t ac[ND];
+        pho_row<ND>(pa + (size_t)q * stride1, D, ac);
+#pragma unroll
+        for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
+        sa = pho_sum<ND>(ac, sa);
+        saa = pho_dot<ND>(ac, ac, saa);
+    }
+}
+
+// a position (converted only after its caller tested it in double) as its integer corner and the bilinear
+// weights of the four pixels (iy, ix), (iy, ix + 1), (iy + 1, ix), (iy + 1, ix + 1).  Returned by value: with
+// iy and ix as reference parameters the compiler orders k_photo's window tests differently.
+struct PhoPos {
+    int iy, ix;
+    double w[4];
+};
+
+__device__ __forceinline__ PhoPos pho_bilin(double py, double px)
+{
+    const double fly = floor(py), flx = floor(px);
+    const int iy = (int)fly, ix = (int)flx;
+    const double fy = py - fly, fx = px - flx;
+    const double gy = 1.0 - fy, gx = 1.0 - fx;
+    return {iy, ix, {gy * gx, gy * fx, fy * gx, fy * fx}};
 }
 
 // num and vb of dm_photo_score's rule 5 from the exact sums of one position: S[k] = sum P_k, A[k] =

@@ -36,7 +36,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "dm_photo.h"      // PHO_*, pho_finite, pho_row, pho_dot, pho_sum: shared with dm_photo_refine.hip
+#include "dm_photo.h"
 
 // grid: tiles_x * tiles_y workgroups of PHO_TX x PHO_TY cells.  ND = (r + 2) / 2 dwords per row.
 template <int ND>
@@ -46,38 +46,31 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_photo(const uint8_t *img1, s
                                                          int ox, int r, int reject, double min_score, double *maps,
                                                          int M, double *score, double *warped, uint8_t *rejected)
 {
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
-    if (y >= H || x >= W) return;
+    int y, x;
+    if (!pho_cell(tiles_x, H, W, y, x)) return;
     const size_t c = (size_t)y * W + x;
     const double dr = d_row[c], dc = d_col[c];
-    const double NaN = __longlong_as_double(0x7ff8000000000000LL);
-    double s = NaN, wv = NaN;
+    double s = dm_nan(), wv = dm_nan();
     if (pho_finite(dr) && pho_finite(dc)) {
         const int cy = y + oy, cx = x + ox;
         const double py = (double)cy - dr, px = (double)cx - dc;
         // the tests on py and px are made in double: only a position inside the image is converted
         const bool in4 = py >= 0.0 && py < (double)(Hi - 1) && px >= 0.0 && px < (double)(Wi - 1);
         if (in4) {
-            const double fly = floor(py), flx = floor(px);
-            const int iy = (int)fly, ix = (int)flx;
-            const double fy = py - fly, fx = px - flx;
-            const double gy = 1.0 - fy, gx = 1.0 - fx;
-            const double w0 = gy * gx, w1 = gy * fx, w2 = fy * gx, w3 = fy * fx;
+            const PhoPos pos = pho_bilin(py, px);
+            const int iy = pos.iy, ix = pos.ix;
+            const double(&w)[4] = pos.w;
             if (warped) {
                 const uint8_t *q = img2 + (size_t)iy * stride2 + ix;
-                wv = ((w0 * (double)q[0] + w1 * (double)q[1]) + w2 * (double)q[stride2]) + w3 * (double)q[stride2 + 1];
+                wv = ((w[0] * (double)q[0] + w[1] * (double)q[1]) + w[2] * (double)q[stride2]) +
+                     w[3] * (double)q[stride2 + 1];
             }
             const bool win1 = cy >= r && cy <= Hi - 1 - r && cx >= r && cx <= Wi - 1 - r;
             const bool win2 = iy >= r && iy <= Hi - 2 - r && ix >= r && ix <= Wi - 2 - r;
             if (win1 && win2 && (score || reject)) {
                 const int D = 2 * r + 1;
-                uint32_t mask[ND];      // the bytes 0 .. 2r of a row
-#pragma unroll
-                for (int k = 0; k < ND; ++k) {
-                    const int nb = D - 4 * k;      // bytes of the window in dword k: >= 1
-                    mask[k] = nb >= 4 ? 0xffffffffu : (0xffffffffu >> (8 * (4 - nb)));
-                }
+                uint32_t mask[ND];
+                pho_wmask<ND>(D, mask);
                 const uint8_t *pa = img1 + (size_t)(cy - r) * stride1 + (cx - r);
                 const uint8_t *pb = img2 + (size_t)(iy - r) * stride2 + (ix - r);
                 uint32_t sa = 0, saa = 0, S0 = 0, S1 = 0, S2 = 0, S3 = 0, A0 = 0, A1 = 0, A2 = 0, A3 = 0;
@@ -121,33 +114,13 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_photo(const uint8_t *img1, s
                         if (q < D) ap[k] = ac[k];
                     }
                 }
-                const int64_t n = (int64_t)D * D;
-                const int64_t Sa = sa, s0 = S0, s1 = S1, s2 = S2, s3 = S3;
+                const int64_t n = (int64_t)D * D, Sa = sa;
                 const double VA = (double)(n * (int64_t)saa - Sa * Sa);
-                const double CA0 = (double)(n * (int64_t)A0 - Sa * s0), CA1 = (double)(n * (int64_t)A1 - Sa * s1);
-                const double CA2 = (double)(n * (int64_t)A2 - Sa * s2), CA3 = (double)(n * (int64_t)A3 - Sa * s3);
-                const double C00 = (double)(n * (int64_t)B00 - s0 * s0), C01 = (double)(n * (int64_t)B01 - s0 * s1);
-                const double C02 = (double)(n * (int64_t)B02 - s0 * s2), C03 = (double)(n * (int64_t)B03 - s0 * s3);
-                const double C11 = (double)(n * (int64_t)B11 - s1 * s1), C12 = (double)(n * (int64_t)B12 - s1 * s2);
-                const double C13 = (double)(n * (int64_t)B13 - s1 * s3), C22 = (double)(n * (int64_t)B22 - s2 * s2);
-                const double C23 = (double)(n * (int64_t)B23 - s2 * s3), C33 = (double)(n * (int64_t)B33 - s3 * s3);
-                const double num = ((w0 * CA0 + w1 * CA1) + w2 * CA2) + w3 * CA3;
-                double vb = (1.0 * (w0 * w0)) * C00;
-                vb = vb + (2.0 * (w0 * w1)) * C01;
-                vb = vb + (2.0 * (w0 * w2)) * C02;
-                vb = vb + (2.0 * (w0 * w3)) * C03;
-                vb = vb + (1.0 * (w1 * w1)) * C11;
-                vb = vb + (2.0 * (w1 * w2)) * C12;
-                vb = vb + (2.0 * (w1 * w3)) * C13;
-                vb = vb + (1.0 * (w2 * w2)) * C22;
-                vb = vb + (2.0 * (w2 * w3)) * C23;
-                vb = vb + (1.0 * (w3 * w3)) * C33;
-                if (VA > 0.0 && vb > 0.0) {
-                    const double t = num / sqrt(VA * vb);
-                    s = t > 1.0 ? 1.0 : (t < -1.0 ? -1.0 : t);
-                } else {
-                    s = 0.0;
-                }
+                const uint32_t S[4] = {S0, S1, S2, S3}, A[4] = {A0, A1, A2, A3};
+                const uint32_t B[10] = {B00, B01, B02, B03, B11, B12, B13, B22, B23, B33};
+                double num, vb;
+                pho_numvb(n, Sa, w, S, A, B, num, vb);
+                s = pho_zncc(VA, num, vb);
             }
         }
     }
@@ -158,7 +131,7 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_photo(const uint8_t *img1, s
         if (rejected) rejected[c] = rej ? 1 : 0;
         if (rej) {
             const size_t cells = (size_t)H * W;
-            for (int m = 0; m < M; ++m) maps[(size_t)m * cells + c] = NaN;
+            for (int m = 0; m < M; ++m) maps[(size_t)m * cells + c] = dm_nan();
         }
     }
 }
@@ -178,14 +151,7 @@ int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_work)
         return dm_fail(DM_ERR_ARG, "null image / disparity / workspace pointer");
-    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
-    if (stride1 < Wi || stride2 < Wi)
-        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
-                     (long long)stride2);
-    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
-    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (const int bad = pho_pair_args(stride1, stride2, Hi, Wi, H, W, oy, ox, radius)) return bad;
     if (flags & ~DM_PHOTO_REJECT) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     const int reject = (flags & DM_PHOTO_REJECT) ? 1 : 0;
     if (reject) {
@@ -201,19 +167,14 @@ int dm_photo_score(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2
     if (!pho_plan(M, H, W))
         return dm_fail(DM_ERR_UNSUPPORTED,
                      "photo score of %d maps of %d x %d cells (at most 65535 maps of 2^31 - 1 cells)", M, H, W);
-    const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
+    int tiles_x;
+    const dim3 grid = pho_grid(H, W, &tiles_x);
     hipStream_t st = (hipStream_t)stream;
 #define PHO_GO(ND_)                                                                                              \
     k_photo<ND_><<<grid, PHO_TX * PHO_TY, 0, st>>>(d_img1, (size_t)stride1, d_img2, (size_t)stride2, Hi, Wi, d_row, \
                                                    d_col, H, W, tiles_x, oy, ox, radius, reject, min_score,        \
                                                    reject ? d_maps : nullptr, M, d_score, d_warped, d_rejected)
-    switch ((radius + 2) / 2) {
-    case 1: PHO_GO(1); break;
-    case 2: PHO_GO(2); break;
-    case 3: PHO_GO(3); break;
-    default: PHO_GO(4); break;
-    }
+    PHO_SWITCH_ND(radius, PHO_GO)
 #undef PHO_GO
     DM_HIP_TRY(hipGetLastError());
     return DM_OK;

@@ -32,39 +32,6 @@
 #define REF_SMAX 3
 #define REF_POSMAX 1073741824.0      // 2^30
 
-// dm_photo_score's rule 5 on the exact sums of one candidate (include/dmstereo.h)
-__device__ __forceinline__ double ref_tail(int64_t n, int64_t Sa, double VA, double w0, double w1, double w2, double w3,
-                                           uint32_t S0, uint32_t S1, uint32_t S2, uint32_t S3, uint32_t A0, uint32_t A1,
-                                           uint32_t A2, uint32_t A3, uint32_t B00, uint32_t B01, uint32_t B02,
-                                           uint32_t B03, uint32_t B11, uint32_t B12, uint32_t B13, uint32_t B22,
-                                           uint32_t B23, uint32_t B33)
-{
-    const int64_t s0 = S0, s1 = S1, s2 = S2, s3 = S3;
-    const double CA0 = (double)(n * (int64_t)A0 - Sa * s0), CA1 = (double)(n * (int64_t)A1 - Sa * s1);
-    const double CA2 = (double)(n * (int64_t)A2 - Sa * s2), CA3 = (double)(n * (int64_t)A3 - Sa * s3);
-    const double C00 = (double)(n * (int64_t)B00 - s0 * s0), C01 = (double)(n * (int64_t)B01 - s0 * s1);
-    const double C02 = (double)(n * (int64_t)B02 - s0 * s2), C03 = (double)(n * (int64_t)B03 - s0 * s3);
-    const double C11 = (double)(n * (int64_t)B11 - s1 * s1), C12 = (double)(n * (int64_t)B12 - s1 * s2);
-    const double C13 = (double)(n * (int64_t)B13 - s1 * s3), C22 = (double)(n * (int64_t)B22 - s2 * s2);
-    const double C23 = (double)(n * (int64_t)B23 - s2 * s3), C33 = (double)(n * (int64_t)B33 - s3 * s3);
-    const double num = ((w0 * CA0 + w1 * CA1) + w2 * CA2) + w3 * CA3;
-    double vb = (1.0 * (w0 * w0)) * C00;
-    vb = vb + (2.0 * (w0 * w1)) * C01;
-    vb = vb + (2.0 * (w0 * w2)) * C02;
-    vb = vb + (2.0 * (w0 * w3)) * C03;
-    vb = vb + (1.0 * (w1 * w1)) * C11;
-    vb = vb + (2.0 * (w1 * w2)) * C12;
-    vb = vb + (2.0 * (w1 * w3)) * C13;
-    vb = vb + (1.0 * (w2 * w2)) * C22;
-    vb = vb + (2.0 * (w2 * w3)) * C23;
-    vb = vb + (1.0 * (w3 * w3)) * C33;
-    if (VA > 0.0 && vb > 0.0) {
-        const double t = num / sqrt(VA * vb);
-        return t > 1.0 ? 1.0 : (t < -1.0 ? -1.0 : t);
-    }
-    return 0.0;
-}
-
 // the parabola through (-1, sm), (0, s0), (1, sp): its peak, clamped to [-0.5, 0.5]; 0 unless it opens downwards
 __device__ __forceinline__ double ref_peak(double sm, double s0, double sp)
 {
@@ -87,12 +54,11 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
     constexpr int NC = 2 * S + 1;                  // candidates a side
     constexpr int K = 2 * S + 2;                   // window shifts a side
     constexpr int NW = ND + (2 * S + 3) / 4;       // dwords of the widest row read: 4 ND + 2 S bytes
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
-    if (y >= H || x >= W) return;
+    int y, x;
+    if (!pho_cell(tiles_x, H, W, y, x)) return;
     const size_t c = (size_t)y * W + x;
     const double dr = d_row[c], dc = d_col[c];
-    const double NaN = __longlong_as_double(0x7ff8000000000000LL);
+    const double NaN = dm_nan();
     double o_row = dr, o_col = dc, o_score = NaN;
     int o_dy = 0, o_dx = 0;
     const int cy = y + oy, cx = x + ox;
@@ -105,11 +71,9 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
         live = py >= -REF_POSMAX && py <= REF_POSMAX && px >= -REF_POSMAX && px <= REF_POSMAX;
     }
     if (live) {
-        const double fly = floor(py), flx = floor(px);
-        const int iy = (int)fly, ix = (int)flx;      // |iy|, |ix| <= 2^30
-        const double fy = py - fly, fx = px - flx;
-        const double gy = 1.0 - fy, gx = 1.0 - fx;
-        const double w0 = gy * gx, w1 = gy * fx, w2 = fy * gx, w3 = fy * fx;
+        const PhoPos pos = pho_bilin(py, px);
+        const int iy = pos.iy, ix = pos.ix;      // |iy|, |ix| <= 2^30
+        const double(&w)[4] = pos.w;
         // the scored candidates: r <= iy + dy <= Hi - r - 2, r <= ix + dx <= Wi - r - 2 (no overflow: Hi, Wi <= 2^30)
         const int dylo = max(-S, r - iy), dyhi = min(S, Hi - r - 2 - iy);
         const int dxlo = max(-S, r - ix), dxhi = min(S, Wi - r - 2 - ix);
@@ -121,22 +85,10 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
             const int64_t n = (int64_t)D * D;
             const int ncand = dxhi - dxlo + 1;           // candidates of a row: 1 .. NC
             const int nbytes = ncand + D;                // bytes of an image row that they need: >= 4
-            uint32_t wmask[ND];      // the bytes 0 .. 2r of a window row
-#pragma unroll
-            for (int k = 0; k < ND; ++k) {
-                const int nb = D - 4 * k;      // bytes of the window in dword k: >= 1
-                wmask[k] = nb >= 4 ? 0xffffffffu : (0xffffffffu >> (8 * (4 - nb)));
-            }
+            uint32_t wmask[ND], sa, saa;
+            pho_wmask<ND>(D, wmask);
             const uint8_t *pa = img1 + (size_t)(cy - r) * stride1 + (cx - r);
-            uint32_t sa = 0, saa = 0;
-            for (int q = 0; q < D; ++q) {
-                uint32_t ac[ND];
-                pho_row<ND>(pa + (size_t)q * stride1, D, ac);
-#pragma unroll
-                for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
-                sa = pho_sum<ND>(ac, sa);
-                saa = pho_dot<ND>(ac, ac, saa);
-            }
+            pho_moments1<ND>(pa, stride1, D, wmask, sa, saa);
             const int64_t Sa = sa;
             const double VA = (double)(n * (int64_t)saa - Sa * Sa);
             for (int dy = dylo; dy <= dyhi; ++dy) {
@@ -208,11 +160,14 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
                 // candidate j of this row: P0 = upper j, P1 = upper j+1, P2 = lower j, P3 = lower j+1
 #pragma unroll
                 for (int j = 0; j < NC; ++j) {
-                    if (j < ncand)
-                        sc[(dy + S) * NC + (dxlo + S + j)] =
-                            ref_tail(n, Sa, VA, w0, w1, w2, w3, St[j], St[j + 1], Sb[j], Sb[j + 1], At[j], At[j + 1],
-                                     Ab[j], Ab[j + 1], Qt[j], Et[j], Dn[j], Ds[j], Qt[j + 1], Dw[j], Dn[j + 1], Qb[j],
-                                     Eb[j], Qb[j + 1]);
+                    if (j < ncand) {
+                        const uint32_t Sj[4] = {St[j], St[j + 1], Sb[j], Sb[j + 1]};
+                        const uint32_t Aj[4] = {At[j], At[j + 1], Ab[j], Ab[j + 1]};
+                        const uint32_t Bj[10] = {Qt[j], Et[j], Dn[j], Ds[j], Qt[j + 1], Dw[j], Dn[j + 1], Qb[j], Eb[j], Qb[j + 1]};
+                        double num, vb;
+                        pho_numvb(n, Sa, w, Sj, Aj, Bj, num, vb);      // dm_photo_score's rule 5, operation for operation
+                        sc[(dy + S) * NC + (dxlo + S + j)] = pho_zncc(VA, num, vb);
+                    }
                 }
             }
             // the winner: the highest score; ties to the smallest dy^2 + dx^2, then the smaller dy, then the smaller dx
@@ -259,12 +214,11 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_refine(const uint8_t *img1, 
 }
 
 // ---- host side ------------------------------------------------------------------------------
-// false for a shape the entry does not take (dm_photo_bytes' limits, and images of at most 2^30 a side)
+// false for a shape the entry does not take
 static bool ref_plan(int32_t Hi, int32_t Wi, int32_t H, int32_t W, int32_t radius, int32_t search)
 {
     if (radius < 1 || radius > PHO_RMAX || search < 1 || search > REF_SMAX) return false;
-    if (Hi < 1 || Wi < 1 || Hi > (1 << 30) || Wi > (1 << 30)) return false;
-    return dm_photo_bytes(1, H, W) != 0;
+    return pho_pair_plan(Hi, Wi, H, W);
 }
 
 extern "C" {
@@ -281,14 +235,7 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_out_row || !d_out_col || !d_work)
         return dm_fail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
-    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
-    if (stride1 < Wi || stride2 < Wi)
-        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
-                     (long long)stride2);
-    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
-    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (const int bad = pho_pair_args(stride1, stride2, Hi, Wi, H, W, oy, ox, radius)) return bad;
     if (search < 1 || search > REF_SMAX) return dm_fail(DM_ERR_ARG, "search must be in [1, %d] (got %d)", REF_SMAX, search);
     if (!(min_gain >= 0.0 && min_gain <= 2.0)) return dm_fail(DM_ERR_ARG, "min_gain must be in [0, 2] (got %g)", min_gain);
     if (flags & ~DM_REFINE_SUBPIX) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
@@ -296,8 +243,8 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
         return dm_fail(DM_ERR_UNSUPPORTED,
                      "photo refine of %d x %d cells on a %d x %d image (at most 2^31 - 1 cells, 2^30 pixels a side)", H,
                      W, Hi, Wi);
-    const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
+    int tiles_x;
+    const dim3 grid = pho_grid(H, W, &tiles_x);
     hipStream_t st = (hipStream_t)stream;
     const int subpix = (flags & DM_REFINE_SUBPIX) ? 1 : 0;
 #define REF_GO(ND_, S_)                                                                                               \
@@ -310,12 +257,7 @@ int dm_photo_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img
     case 2: REF_GO(ND_, 2); break;                                                                                    \
     default: REF_GO(ND_, 3); break;                                                                                   \
     }
-    switch ((radius + 2) / 2) {
-    case 1: REF_GO_S(1); break;
-    case 2: REF_GO_S(2); break;
-    case 3: REF_GO_S(3); break;
-    default: REF_GO_S(4); break;
-    }
+    PHO_SWITCH_ND(radius, REF_GO_S)
 #undef REF_GO_S
 #undef REF_GO
     DM_HIP_TRY(hipGetLastError());

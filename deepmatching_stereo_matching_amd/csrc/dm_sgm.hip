@@ -53,20 +53,6 @@
 
 enum { SGM_DEAD = 0, SGM_FIXED = 1, SGM_FREE = 2 };
 
-// the first nbytes (3 .. 4 NW) bytes at p as NW little-endian dwords, zero from nbytes on.  Reads nothing
-// outside [p, p + nbytes).
-template <int NW>
-__device__ __forceinline__ void sgm_rowz(const uint8_t *p, int nbytes, uint32_t (&d)[NW])
-{
-    if (nbytes < 4) {
-        d[0] = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16);
-#pragma unroll
-        for (int k = 1; k < NW; ++k) d[k] = 0u;
-        return;
-    }
-    pho_rowz<NW>(p, nbytes, d);
-}
-
 __device__ __forceinline__ int sgm_cost_of(double score) { return (int)rint((1.0 - score) * 1024.0); }
 
 // grid: tiles_x * tiles_y workgroups of PHO_TX x PHO_TY cells.  ND = (r + 2) / 2 dwords per window row.
@@ -79,9 +65,8 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_sgm_cost(const uint8_t *img1
 {
     constexpr int NC = 2 * S + 1, L = NC * NC;
     constexpr int NW = ND + (2 * S + 3) / 4;       // dwords of the widest row read: 4 ND + 2 S bytes
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
-    if (y >= H || x >= W) return;
+    int y, x;
+    if (!pho_cell(tiles_x, H, W, y, x)) return;
     const size_t HW = (size_t)H * W, c = (size_t)y * W + x;
     const double dr = d_row[c], dc = d_col[c];
     const int cy = y + oy, cx = x + ox;
@@ -120,18 +105,10 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_sgm_cost(const uint8_t *img1
     const int64_t n = (int64_t)D * D;
     const int ncand = axhi - axlo + 1;           // candidates of a row: 1 .. NC
     const int nbytes = ncand + D - 1;            // bytes of an image row that they need: >= 3
-    uint32_t wmask[ND];
+    uint32_t wmask[ND], sa, saa;
     pho_wmask<ND>(D, wmask);
     const uint8_t *pa = img1 + (size_t)(cy - r) * stride1 + (cx - r);
-    uint32_t sa = 0, saa = 0;
-    for (int q = 0; q < D; ++q) {
-        uint32_t ac[ND];
-        pho_row<ND>(pa + (size_t)q * stride1, D, ac);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
-        sa = pho_sum<ND>(ac, sa);
-        saa = pho_dot<ND>(ac, ac, saa);
-    }
+    pho_moments1<ND>(pa, stride1, D, wmask, sa, saa);
     const int64_t Sa = sa;
     const double VA = (double)(n * (int64_t)saa - Sa * Sa);
     for (int ay = -S; ay <= S; ++ay) {
@@ -147,7 +124,7 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_sgm_cost(const uint8_t *img1
         for (int j = 0; j < NC; ++j) St[j] = Qt[j] = At[j] = 0;
         for (int q = 0; q < D; ++q) {
             uint32_t raw[NW], ac[ND];
-            sgm_rowz<NW>(pb + (size_t)q * stride2, nbytes, raw);
+            pho_rowz<NW, true>(pb + (size_t)q * stride2, nbytes, raw);
             pho_row<ND>(pa + (size_t)q * stride1, D, ac);
 #pragma unroll
             for (int k = 0; k < ND; ++k) ac[k] &= wmask[k];
@@ -309,9 +286,8 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_sgm_pick(const uint8_t *img1
                                                             double *out_col, double *score, int8_t *shift)
 {
     const int NC = 2 * S + 1, L = NC * NC;
-    const int tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int y = tile_y * PHO_TY + (int)(threadIdx.x / PHO_TX), x = tile_x * PHO_TX + (int)(threadIdx.x % PHO_TX);
-    if (y >= H || x >= W) return;
+    int y, x;
+    if (!pho_cell(tiles_x, H, W, y, x)) return;
     const size_t HW = (size_t)H * W, c = (size_t)y * W + x;
     const double dr = d_row[c], dc = d_col[c];
     double o_row = dr, o_col = dc, o_score = dm_nan();
@@ -361,7 +337,7 @@ __global__ __launch_bounds__(PHO_TX *PHO_TY) void k_sgm_pick(const uint8_t *img1
 static size_t sgm_bytes(int32_t H, int32_t W, int32_t search, int32_t paths)
 {
     if (search < 1 || search > SGM_SMAX || (paths != 4 && paths != 8)) return 0;
-    if (dm_photo_bytes(1, H, W) == 0) return 0;
+    if (!pho_pair_plan(1, 1, H, W)) return 0;      // (the map's side of the limits: this size has no image)
     const size_t L = (size_t)(2 * search + 1) * (2 * search + 1), per = 16 + 6 * L + 1, HW = (size_t)H * (size_t)W;
     if (HW > (SIZE_MAX - 15) / per) return 0;      // checked before multiplying
     return (HW * per + 15) & ~(size_t)15;
@@ -378,21 +354,14 @@ int dm_sgm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2,
 {
     if (!d_img1 || !d_img2 || !d_row || !d_col || !d_out_row || !d_out_col || !d_work)
         return dm_fail(DM_ERR_ARG, "null image / disparity / output / workspace pointer");
-    if (Hi < 1 || Wi < 1) return dm_fail(DM_ERR_ARG, "bad image shape Hi=%d Wi=%d", Hi, Wi);
-    if (stride1 < Wi || stride2 < Wi)
-        return dm_fail(DM_ERR_ARG, "row stride below the image width %d (got %lld, %lld)", Wi, (long long)stride1,
-                     (long long)stride2);
-    if (H < 1 || W < 1) return dm_fail(DM_ERR_ARG, "bad map shape H=%d W=%d", H, W);
-    if (oy < -PHO_OFFMAX || oy > PHO_OFFMAX || ox < -PHO_OFFMAX || ox > PHO_OFFMAX)
-        return dm_fail(DM_ERR_ARG, "offset must be in [-2^30, 2^30] (got %d, %d)", oy, ox);
-    if (radius < 1 || radius > PHO_RMAX) return dm_fail(DM_ERR_ARG, "radius must be in [1, %d] (got %d)", PHO_RMAX, radius);
+    if (const int bad = pho_pair_args(stride1, stride2, Hi, Wi, H, W, oy, ox, radius)) return bad;
     if (search < 1 || search > SGM_SMAX) return dm_fail(DM_ERR_ARG, "search must be in [1, %d] (got %d)", SGM_SMAX, search);
     if (paths != 4 && paths != 8) return dm_fail(DM_ERR_ARG, "paths must be 4 or 8 (got %d)", paths);
     if (p1 < 0 || p1 > p2 || p2 > SGM_PMAX)
         return dm_fail(DM_ERR_ARG, "penalties must satisfy 0 <= p1 <= p2 <= %d (got %d, %d)", SGM_PMAX, p1, p2);
     if (flags & ~DM_SGM_SUBPIX) return dm_fail(DM_ERR_ARG, "unknown flags 0x%x", flags);
     const size_t bytes = sgm_bytes(H, W, search, paths);
-    if (!bytes || Hi > (1 << 30) || Wi > (1 << 30))
+    if (!bytes || !pho_pair_plan(Hi, Wi, H, W))
         return dm_fail(DM_ERR_UNSUPPORTED,
                      "sgm refine of %d x %d cells on a %d x %d image (at most 2^31 - 1 cells, 2^30 pixels a side)", H, W,
                      Hi, Wi);
@@ -401,8 +370,8 @@ int dm_sgm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2,
     uint32_t *Ssum = (uint32_t *)((char *)d_work + 16 * HW);
     uint16_t *C = (uint16_t *)((char *)d_work + (16 + 4 * L) * HW);
     uint8_t *state = (uint8_t *)d_work + (16 + 6 * L) * HW;
-    const int tiles_x = (W + PHO_TX - 1) / PHO_TX, tiles_y = (H + PHO_TY - 1) / PHO_TY;      // tiles_x tiles_y < 2^31
-    const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y);
+    int tiles_x;
+    const dim3 grid = pho_grid(H, W, &tiles_x);
     hipStream_t st = (hipStream_t)stream;
     DM_HIP_TRY(hipMemsetAsync(Ssum, 0, 4 * L * HW, st));
 #define SGM_COST(ND_, S_)                                                                                                \
@@ -414,12 +383,7 @@ int dm_sgm_refine(const uint8_t *d_img1, int64_t stride1, const uint8_t *d_img2,
     case 2: SGM_COST(ND_, 2); break;                                                                                     \
     default: SGM_COST(ND_, 3); break;                                                                                    \
     }
-    switch ((radius + 2) / 2) {
-    case 1: SGM_COST_S(1); break;
-    case 2: SGM_COST_S(2); break;
-    case 3: SGM_COST_S(3); break;
-    default: SGM_COST_S(4); break;
-    }
+    PHO_SWITCH_ND(radius, SGM_COST_S)
 #undef SGM_COST_S
 #undef SGM_COST
     DM_HIP_TRY(hipGetLastError());

@@ -724,6 +724,20 @@ def stitch(match, n, h0, w0, stride, modes, stream=None):
     return dmap, score
 
 
+def stitch_any(fwd, bwd, n, h0, w0, stride, modes, consistency, merge, merge_min_count=1, stitcher=None, merger=None):
+    """The stitch that the ``consistency`` and ``merge`` keywords of ImageCutSolver / solve_image_sharded
+    select -> the head of chain.Chain.layout as a tuple: stitch_merge with ``merge`` (without its err when
+    only one direction was solved), else stitch_fb with ``consistency``, else stitch.  ``fwd``: the solved
+    tiles, ``bwd``: those of the other direction, None unless ``consistency`` is set.  ``stitcher`` /
+    ``merger`` replace stitch or stitch_fb / stitch_merge (the hooks of solve_image_sharded)."""
+    if merge is not None:
+        maps = (merger or stitch_merge)(fwd, bwd, n, h0, w0, stride, modes, consistency, merge, merge_min_count)
+        return tuple(m for m in maps if m is not None)      # a one-direction merge has no err
+    if consistency is not None:
+        return (stitcher or stitch_fb)(fwd, bwd, n, h0, w0, stride, modes, consistency)
+    return (stitcher or stitch)(fwd, n, h0, w0, stride, modes)
+
+
 # ---- argument plumbing of the d_map stages below (fill_holes ... lsm_refine) -------------------
 def _int_in(x, lo, hi, msg, got=None):
     """int(x) of an int (not a bool) in [lo, hi]; else ValueError(msg % (got or x,))."""
@@ -1046,6 +1060,77 @@ def _photo_image(img, device):
     return t
 
 
+def _pair_images(img1, img2, dev):
+    """The pair as _photo_image tensors (a, b) of one shape; else ValueError."""
+    a, b = _photo_image(img1, dev), _photo_image(img2, dev)
+    if a.shape != b.shape:
+        raise ValueError('img1 and img2 must have the same shape')
+    return a, b
+
+
+def _held_planes(d_row, d_col):
+    """The two planes as contiguous tensors (a contiguous plane is read from where it is: in place it
+    aliases the output, which the kernels allow).  The caller holds them until the launch: a copy must
+    not be freed before it."""
+    return d_row.contiguous(), d_col.contiguous()
+
+
+def _plane_mask(mask, d_row):
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.device == d_row.device and
+                                 mask.dtype in (torch.uint8, torch.bool) and mask.shape == d_row.shape):
+        raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
+
+
+def _plane_out(out, d_row):
+    if out is not None and not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
+            isinstance(o, torch.Tensor) and o.device == d_row.device and o.dtype == torch.float64 and
+            o.shape == d_row.shape and o.is_contiguous() for o in out)):
+        raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
+
+
+def _rematch(entry, bytes_call, img1, img2, d_row, d_col, offset, mask, out, scalars, return_score, aux_shape, stream,
+             unsupported_msg):
+    """The body of the plane re-matching entries (photo_refine, lsm_refine, sgm_refine), whose C entries
+    share one argument layout: the pair, the planes, the map shape and the offset, then the stage's
+    ``scalars``, then mask, the two output planes, the score, the int8 plane of ``aux_shape`` (None: not
+    asked for), the workspace and the stream.  ``bytes_call(lib, Hi, Wi, H, W)``: the workspace size;
+    ``unsupported_msg``: NotImplementedError's text, a template over H, W, Hi, Wi.
+    -> (d_row', d_col', score or None, aux or None)."""
+    dev = _planes_device(d_row, d_col)
+    oy, ox = _offset(offset)
+    _plane_mask(mask, d_row)
+    _plane_out(out, d_row)
+    H, W = d_row.shape
+    with _on(stream):
+        a, b = _pair_images(img1, img2, dev)
+        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
+                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
+        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
+        aux = torch.empty(aux_shape, dtype=torch.int8, device=dev) if aux_shape is not None else None
+        if H and W:
+            if not a.numel():
+                raise ValueError('empty image')
+            lib = L.load()
+            Hi, Wi = a.shape
+            work = _workspace(bytes_call(lib, Hi, Wi, H, W), dev, unsupported_msg % dict(H=H, W=W, Hi=Hi, Wi=Wi))
+            m = None if mask is None else mask.to(torch.uint8).contiguous()
+            rows, cols = _held_planes(d_row, d_col)
+            L.check(getattr(lib, entry)(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), Hi, Wi, L.ptr(rows), L.ptr(cols),
+                                        H, W, int(oy), int(ox), *scalars, L.ptr(m), L.ptr(o_row), L.ptr(o_col),
+                                        L.ptr(score), L.ptr(aux), L.ptr(work), L.stream_handle()), entry)
+    return o_row, o_col, score, aux
+
+
+def _plane_stage(fn, img1, img2, d_map, modes, holes, *args, **kw):
+    """A plane re-matching stage of the chain on the stitched d_map [len(modes)][H][W], in place: ``fn`` on
+    the two elevation planes, of the cells that ``holes`` marks in either (None: every cell).
+    -> (d_map, score, the stage's int8 plane)."""
+    ir, ic = refine_planes(modes)
+    mask = None if holes is None else (holes[ir] | holes[ic])
+    _, _, score, aux = fn(img1, img2, d_map[ir], d_map[ic], *args, mask=mask, out=(d_map[ir], d_map[ic]), **kw)
+    return d_map, score, aux
+
+
 def photo_planes(modes):
     """Indices (row, column) of 'elevation2' and 'elevation' in a degree_map_mode list: the planes
     ``photo=`` reads.  ValueError when one is missing."""
@@ -1088,9 +1173,7 @@ def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps
             raise ValueError('return_rejected needs min_score')
     H, W = d_row.shape
     with _on(stream):
-        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
-        if a.shape != b.shape:
-            raise ValueError('img1 and img2 must have the same shape')
+        a, b = _pair_images(img1, img2, dev)
         score = torch.empty((H, W), dtype=torch.float64, device=dev)
         warped = torch.empty((H, W), dtype=torch.float64, device=dev) if return_warped else None
         rejected = torch.empty((H, W), dtype=torch.uint8, device=dev) if return_rejected else None
@@ -1108,7 +1191,7 @@ def photo_score(img1, img2, d_row, d_col, radius, offset=0, min_score=None, maps
             lib = L.load()
             work = _workspace(lib.dm_photo_bytes(M, H, W), dev,
                               'photo_score does not take %d maps of %d x %d cells' % (M, H, W))
-            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
+            rows, cols = _held_planes(d_row, d_col)
             L.check(lib.dm_photo_score(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
                                        L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
                                        radius, L.DM_PHOTO_REJECT if min_score is not None else 0,
@@ -1183,43 +1266,14 @@ def photo_refine(img1, img2, d_row, d_col, radius, search, offset=0, min_gain=0.
     contiguous), else new tensors.
     -> (d_row', d_col'); then, when asked for, the float64 score of the position kept (NaN for a
     skipped cell) and the int8 shift [2][H][W] (dy, dx) are appended."""
-    dev = _planes_device(d_row, d_col)
+    _planes_device(d_row, d_col)
     radius, search, min_gain = refine_params((radius, search, min_gain))
-    oy, ox = _offset(offset)
-    if mask is not None:
-        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
-                mask.shape == d_row.shape):
-            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
-                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
-                o.shape == d_row.shape and o.is_contiguous() for o in out)):
-            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
-    H, W = d_row.shape
-    with _on(stream):
-        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
-        if a.shape != b.shape:
-            raise ValueError('img1 and img2 must have the same shape')
-        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
-                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
-        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
-        shift = torch.empty((2, H, W), dtype=torch.int8, device=dev) if return_shift else None
-        if H and W:
-            if not a.numel():
-                raise ValueError('empty image')
-            lib = L.load()
-            work = _workspace(lib.dm_photo_refine_bytes(a.shape[0], a.shape[1], H, W, radius, search), dev,
-                              'photo_refine does not take %d x %d cells on a %d x %d image' %
-                              (H, W, a.shape[0], a.shape[1]))
-            m = None if mask is None else mask.to(torch.uint8).contiguous()
-            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
-            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
-            L.check(lib.dm_photo_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                        L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
-                                        radius, search, min_gain, L.DM_REFINE_SUBPIX if subpix else 0, L.ptr(m),
-                                        L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
-                                        L.stream_handle()), 'dm_photo_refine')
-    return (o_row, o_col) + ((score,) if return_score else ()) + ((shift,) if return_shift else ())
+    res = _rematch('dm_photo_refine', lambda lib, Hi, Wi, H, W: lib.dm_photo_refine_bytes(Hi, Wi, H, W, radius, search),
+                   img1, img2, d_row, d_col, offset, mask, out,
+                   (radius, search, min_gain, L.DM_REFINE_SUBPIX if subpix else 0), return_score,
+                   (2,) + tuple(d_row.shape) if return_shift else None, stream,
+                   'photo_refine does not take %(H)d x %(W)d cells on a %(Hi)d x %(Wi)d image')
+    return tuple(t for t in res if t is not None)
 
 
 def refine_stage(img1, img2, d_map, modes, refine, offset, holes=None):
@@ -1227,12 +1281,8 @@ def refine_stage(img1, img2, d_map, modes, refine, offset, holes=None):
     the fill and before the smoothing.  ``holes``: the fill's uint8 mask [len(modes)][H][W] --
     only the cells that were filled in the row or in the column plane are refined
     (refine_where='filled') -- or None: every cell.  -> (d_map, score, int8 shift [2][H][W])."""
-    ir, ic = refine_planes(modes)
-    mask = None if holes is None else (holes[ir] | holes[ic])
-    d_row, d_col, score, shift = photo_refine(img1, img2, d_map[ir], d_map[ic], refine[0], refine[1], offset=offset,
-                                              min_gain=refine[2], mask=mask, out=(d_map[ir], d_map[ic]),
-                                              return_score=True, return_shift=True)
-    return d_map, score, shift
+    return _plane_stage(photo_refine, img1, img2, d_map, modes, holes, refine[0], refine[1], offset=offset,
+                        min_gain=refine[2], return_score=True, return_shift=True)
 
 
 def lsm_params(lsm):
@@ -1266,42 +1316,13 @@ def lsm_refine(img1, img2, d_row, d_col, radius, iters, offset=0, max_move=1.0, 
     accepted cell, else of the start; NaN for a cell that was not scored) and the int8 status
     [H][W] are appended: ``iters`` accepted, 0 skipped, -1 no texture (a singular system or a flat
     patch), -2 left the image or the square, -3 not better."""
-    dev = _planes_device(d_row, d_col)
+    _planes_device(d_row, d_col)
     radius, iters, max_move = lsm_params((radius, iters, max_move))
-    oy, ox = _offset(offset)
-    if mask is not None:
-        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
-                mask.shape == d_row.shape):
-            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
-                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
-                o.shape == d_row.shape and o.is_contiguous() for o in out)):
-            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
-    H, W = d_row.shape
-    with _on(stream):
-        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
-        if a.shape != b.shape:
-            raise ValueError('img1 and img2 must have the same shape')
-        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
-                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
-        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
-        status = torch.empty((H, W), dtype=torch.int8, device=dev) if return_status else None
-        if H and W:
-            if not a.numel():
-                raise ValueError('empty image')
-            lib = L.load()
-            work = _workspace(lib.dm_lsm_refine_bytes(a.shape[0], a.shape[1], H, W, radius, iters), dev,
-                              'lsm_refine does not take %d x %d cells on a %d x %d image' %
-                              (H, W, a.shape[0], a.shape[1]))
-            m = None if mask is None else mask.to(torch.uint8).contiguous()
-            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernel allows)
-            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
-            L.check(lib.dm_lsm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                      L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
-                                      radius, iters, max_move, 0, L.ptr(m), L.ptr(o_row), L.ptr(o_col),
-                                      L.ptr(score), L.ptr(status), L.ptr(work), L.stream_handle()), 'dm_lsm_refine')
-    return (o_row, o_col) + ((score,) if return_score else ()) + ((status,) if return_status else ())
+    res = _rematch('dm_lsm_refine', lambda lib, Hi, Wi, H, W: lib.dm_lsm_refine_bytes(Hi, Wi, H, W, radius, iters),
+                   img1, img2, d_row, d_col, offset, mask, out, (radius, iters, max_move, 0), return_score,
+                   tuple(d_row.shape) if return_status else None, stream,
+                   'lsm_refine does not take %(H)d x %(W)d cells on a %(Hi)d x %(Wi)d image')
+    return tuple(t for t in res if t is not None)
 
 
 def lsm_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
@@ -1309,12 +1330,8 @@ def lsm_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
     refine stage and before the smoothing.  ``holes``: the fill's uint8 mask [len(modes)][H][W] --
     only the cells that were filled in the row or in the column plane are matched
     (lsm_where='filled') -- or None: every cell.  -> (d_map, score, int8 status [H][W])."""
-    ir, ic = refine_planes(modes)
-    mask = None if holes is None else (holes[ir] | holes[ic])
-    d_row, d_col, score, status = lsm_refine(img1, img2, d_map[ir], d_map[ic], lsm[0], lsm[1], offset=offset,
-                                             max_move=lsm[2], mask=mask, out=(d_map[ir], d_map[ic]),
-                                             return_score=True, return_status=True)
-    return d_map, score, status
+    return _plane_stage(lsm_refine, img1, img2, d_map, modes, holes, lsm[0], lsm[1], offset=offset, max_move=lsm[2],
+                        return_score=True, return_status=True)
 
 
 def sgm_params(sgm):
@@ -1356,42 +1373,22 @@ def sgm_refine(img1, img2, d_row, d_col, radius, search, p1, p2, paths=8, offset
     -> (d_row', d_col'); then, when asked for, the float64 score of the label kept (NaN for a dead
     cell, an anchor and a cell without a scored label) and the int8 shift [2][H][W] (ay, ax) are
     appended."""
-    dev = _planes_device(d_row, d_col)
-    radius, search, q1, q2, paths = sgm_params((radius, search, p1, p2, paths))
-    oy, ox = _offset(offset)
-    if mask is not None:
-        if not (isinstance(mask, torch.Tensor) and mask.device == dev and mask.dtype in (torch.uint8, torch.bool) and
-                mask.shape == d_row.shape):
-            raise ValueError('mask must be a uint8 or bool tensor of the planes\' shape on their device')
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2 and all(
-                isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and
-                o.shape == d_row.shape and o.is_contiguous() for o in out)):
-            raise ValueError('out must be a pair of contiguous float64 tensors of the planes\' shape on their device')
-    H, W = d_row.shape
-    with _on(stream):
-        a, b = _photo_image(img1, dev), _photo_image(img2, dev)
-        if a.shape != b.shape:
-            raise ValueError('img1 and img2 must have the same shape')
-        o_row, o_col = out if out is not None else (torch.empty((H, W), dtype=torch.float64, device=dev),
-                                                    torch.empty((H, W), dtype=torch.float64, device=dev))
-        score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
-        shift = torch.empty((2, H, W), dtype=torch.int8, device=dev) if return_shift else None
-        if H and W:
-            if not a.numel():
-                raise ValueError('empty image')
-            lib = L.load()
-            work = _workspace(lib.dm_sgm_bytes(H, W, search, paths), dev,
-                              'sgm_refine does not take %d x %d cells' % (H, W))
-            m = None if mask is None else mask.to(torch.uint8).contiguous()
-            # (a contiguous plane is read from where it is: in place it aliases `out`, which the kernels allow)
-            rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
-            L.check(lib.dm_sgm_refine(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), a.shape[0], a.shape[1],
-                                      L.ptr(rows), L.ptr(cols), H, W, int(oy), int(ox),
-                                      radius, search, paths, q1, q2, L.DM_SGM_SUBPIX if subpix else 0, L.ptr(m),
-                                      L.ptr(o_row), L.ptr(o_col), L.ptr(score), L.ptr(shift), L.ptr(work),
-                                      L.stream_handle()), 'dm_sgm_refine')
-    return (o_row, o_col) + ((score,) if return_score else ()) + ((shift,) if return_shift else ())
+    _planes_device(d_row, d_col)
+    return _sgm_rematch(img1, img2, d_row, d_col, sgm_params((radius, search, p1, p2, paths)), offset=offset,
+                        subpix=subpix, mask=mask, out=out, return_score=return_score, return_shift=return_shift,
+                        stream=stream)
+
+
+def _sgm_rematch(img1, img2, d_row, d_col, sgm, offset=0, subpix=True, mask=None, out=None, return_score=False,
+                 return_shift=False, stream=None):
+    """sgm_refine with its parameters as sgm_params' tuple (the penalties as ints in units of 1/1024)."""
+    radius, search, q1, q2, paths = sgm
+    res = _rematch('dm_sgm_refine', lambda lib, Hi, Wi, H, W: lib.dm_sgm_bytes(H, W, search, paths),
+                   img1, img2, d_row, d_col, offset, mask, out,
+                   (radius, search, paths, q1, q2, L.DM_SGM_SUBPIX if subpix else 0), return_score,
+                   (2,) + tuple(d_row.shape) if return_shift else None, stream,
+                   'sgm_refine does not take %(H)d x %(W)d cells')
+    return tuple(t for t in res if t is not None)
 
 
 def sgm_stage(img1, img2, d_map, modes, sgm, offset, holes=None):
@@ -1400,12 +1397,8 @@ def sgm_stage(img1, img2, d_map, modes, sgm, offset, holes=None):
     1/1024).  ``holes``: the fill's uint8 mask [len(modes)][H][W] -- only the cells that were filled
     in the row or in the column plane are matched again, every other cell is an anchor
     (sgm_where='filled') -- or None: every cell.  -> (d_map, score, int8 shift [2][H][W])."""
-    ir, ic = refine_planes(modes)
-    mask = None if holes is None else (holes[ir] | holes[ic])
-    d_row, d_col, score, shift = sgm_refine(img1, img2, d_map[ir], d_map[ic], sgm[0], sgm[1], sgm[2] / 1024.0,
-                                            sgm[3] / 1024.0, paths=sgm[4], offset=offset, mask=mask,
-                                            out=(d_map[ir], d_map[ic]), return_score=True, return_shift=True)
-    return d_map, score, shift
+    return _plane_stage(_sgm_rematch, img1, img2, d_map, modes, holes, sgm, offset=offset, return_score=True,
+                        return_shift=True)
 
 
 # ---- disparity priors (csrc/dm_prior.hip; include/dmstereo.h has the definitions) ----------------
@@ -1492,7 +1485,7 @@ def tile_prior(d_row, d_col, origins, h0, w0, e, scale=2, stream=None):
         T = len(o)
         q = torch.empty((T, 2), dtype=torch.int32, device=dev)
         valid = torch.empty((T,), dtype=torch.uint8, device=dev)
-        rows, cols = d_row.contiguous(), d_col.contiguous()      # held until the launch: a copy must not be freed before it
+        rows, cols = _held_planes(d_row, d_col)
         L.check(L.load().dm_tile_prior(L.ptr(rows), L.ptr(cols), d_row.shape[0],
                                        d_row.shape[1], L.ptr(o), T, h0, w0, e, int(scale), L.ptr(q), L.ptr(valid),
                                        L.stream_handle()), 'dm_tile_prior')

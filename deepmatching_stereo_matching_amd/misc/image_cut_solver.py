@@ -123,6 +123,7 @@ class ImageCutSolver():
                                  median=median, median_weight=median_weight, photo=photo, refine=refine,
                                  refine_where=refine_where, lsm=lsm, lsm_where=lsm_where, sgm=sgm,
                                  sgm_where=sgm_where)
+        self._sgm_given = sgm      # the shard path parses the keyword itself: it gets what this solver was given
         for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
                      'refine_where', 'lsm', 'lsm_where', 'sgm', 'sgm_where'):
             setattr(self, name, getattr(self.chain, name))
@@ -239,31 +240,15 @@ class ImageCutSolver():
                                              median_weight=self.median_weight, photo=self.photo,
                                              refine=self.refine, refine_where=self.refine_where,
                                              lsm=self.lsm, lsm_where=self.lsm_where,
-                                             sgm=self._sgm_keyword(), sgm_where=self.sgm_where,
+                                             sgm=self._sgm_given, sgm_where=self.sgm_where,
                                              prior=self.prior, coarse=self.coarse)
         if self.prior is not None or self.coarse is not None:
             maps = self._stitch_prior(args, n, origins)
-        elif self.merge is not None:
-            if self.consistency is not None:
-                fwd, bwd = engine.solve_tiles_bidir(*args)
-            else:
-                fwd, bwd = engine.solve_tiles(*args), None
-            maps = engine.stitch_merge(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency,
-                                       self.merge, self.merge_min_count)
-            maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
-        elif self.consistency is not None:
-            fwd, bwd = engine.solve_tiles_bidir(*args)
-            maps = engine.stitch_fb(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency)
         else:
-            match = engine.solve_tiles(*args)
-            maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
+            fwd, bwd = engine.solve_tiles_bidir(*args) if self.consistency is not None else (engine.solve_tiles(*args), None)
+            maps = engine.stitch_any(fwd, bwd, n, h0, w0, self.stride, self.degree_map_mode, self.consistency,
+                                     self.merge, self.merge_min_count)
         return self.chain.run(maps, self.img1, self.img2, self.exclusive_pix, self.consistency, self.merge)
-
-    def _sgm_keyword(self):
-        """self.sgm (parsed: the penalties in units of 1/1024) as the keyword it was given as."""
-        if self.sgm is None:
-            return None
-        return (self.sgm[0], self.sgm[1], self.sgm[2] / 1024.0, self.sgm[3] / 1024.0, self.sgm[4])
 
     def _stitch_prior(self, args, n, origins):
         """The stitched maps of a solve with priors (self.prior or self.coarse) -> the head of the chain's
@@ -288,12 +273,9 @@ class ImageCutSolver():
                                            consistency=self.consistency)
             match, q_eff, err = res[0], res[1], (res[2] if len(res) > 2 else None)
         self._prior_dev = (q_eff, valid)
-        if self.merge is not None:
-            maps = engine.stitch_merge(match, None, n, h0, w0, self.stride, self.degree_map_mode, None, self.merge,
-                                       self.merge_min_count)
-            return tuple(m for m in maps if m is not None)
-        maps = engine.stitch(match, n, h0, w0, self.stride, self.degree_map_mode)
-        if err is not None:      # the stitch of a tile's score row, fed with the error
+        maps = engine.stitch_any(match, None, n, h0, w0, self.stride, self.degree_map_mode, None, self.merge,
+                                 self.merge_min_count)
+        if err is not None and self.merge is None:      # the stitch of a tile's score row, fed with the error
             maps += (engine.stitch(torch.stack([err, err, err], 1), n, h0, w0, self.stride, ['elevation'])[1],)
         return maps
 

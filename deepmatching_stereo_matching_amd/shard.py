@@ -484,17 +484,9 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     if match is None:
         maps = None
     else:
-        if merge is not None:
-            fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
-            maps = (merger or engine.stitch_merge)(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes),
-                                                   consistency, merge, merge_min_count)
-            maps = tuple(m for m in maps if m is not None)      # a one-direction merge has no err
-        elif consistency is not None:
-            stitch = stitcher or engine.stitch_fb
-            maps = stitch(match[:T], match[T:], n, image_size[0], image_size[1], stride, list(modes), consistency)
-        else:
-            stitch = stitcher or engine.stitch
-            maps = stitch(match, n, image_size[0], image_size[1], stride, list(modes))
+        fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
+        maps = engine.stitch_any(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes), consistency, merge,
+                                 merge_min_count, stitcher=stitcher, merger=merger)
         maps = post.run(maps, pair[0], pair[1], (window_size - 1) // 2, consistency, merge, filler=filler,
                         speckler=speckler, smoother=smoother, medianer=medianer, photoer=photoer, refiner=refiner,
                         lsmer=lsmer, sgmer=sgmer)

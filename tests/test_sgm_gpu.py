@@ -152,6 +152,49 @@ def test_lattice_covers_the_settings():
         assert {c[1] for c in cases if c[0] == shape} >= set(RADII)
 
 
+def tile_edge_case(r, s):
+    """(img1, img2, d_row, d_col, (oy, ox), mask): 9 x 33 cells -- one past the 8-row and the 32-column tile -- on
+    a 24 x 48 image.  The offset r - 1 puts the img1 windows of the first row and column of cells one pixel outside
+    the image (a 15-pixel window leaves no room to do the same at the other end: 24 = 9 + 15, 48 = 33 + 15), so the
+    last row and column of cells claim the position Hi - r - 1 / Wi - r - 1 instead: their img2 windows leave the
+    image for every label but those with a negative step, and with s = 1 the last column scores one label a row
+    (at radius 1 the 3-byte row).  One cell is NaN; the mask holds both values."""
+    H, W, Hi, Wi = 9, 33, 24, 48
+    oy = ox = r - 1
+    a, b = stereo_pair(Hi, Wi, seed=10 * r + s, dx=2)
+    rng = np.random.default_rng(100 * r + s)
+    dr = rng.integers(-6, 7, (H, W)) / 4.0
+    dc = 2.0 + rng.integers(-6, 7, (H, W)) / 4.0
+    dr[H - 1, :] = float(oy + H - 1 - (Hi - r - 1))
+    dc[:, W - 1] = float(ox + W - 1 - (Wi - r - 1))
+    dr[4, 16] = np.nan
+    mask = (rng.uniform(size=(H, W)) < 0.8).astype(np.uint8)
+    assert mask.min() == 0 and mask.max() == 1
+    return a, b, np.ascontiguousarray(dr), np.ascontiguousarray(dc), (oy, ox), mask
+
+
+@pytest.mark.parametrize('s', [1, 2, 3])
+@pytest.mark.parametrize('r', [1, 2, 4, 7])
+def test_every_cost_kernel_instance(r, s):
+    """Every (dwords per window row, label count) instance of k_sgm_cost -- radius 4 is the three-dword row, which
+    RADII has not -- on a map that crosses the tile edges by one cell, from images that are views of row stride 64."""
+    a, b, dr, dc, off, mask = tile_edge_case(r, s)
+    costs = sgm_costs(a, b, dr, dc, r, s, off, mask)
+    free, nsc = costs['state'] == 2, costs['scored'].sum(axis=2)
+    assert (costs['state'] == 0).sum() == 1 and (costs['state'] == 1).any()      # the NaN cell, the anchors
+    assert not costs['scored'][0].any() and not costs['scored'][:, 0].any()       # the img1 window leaves the image
+    for edge in (np.s_[-1, :], np.s_[:, -1]):                                     # some labels' img2 windows do
+        assert (nsc[edge][free[edge]] <= s * (2 * s + 1)).all() and (nsc[edge][free[edge]] > 0).any()
+    assert (nsc[1:-1, 1:-1][free[1:-1, 1:-1]] == (2 * s + 1) ** 2).any()
+    want = sgm_solve(costs, dr, dc, q1024(0.25), q1024(1.0), 8, True)
+    ta, tb = strided(a, 16), strided(b, 16)
+    assert ta.stride(0) == tb.stride(0) == 64 and tuple(ta.shape) == (24, 48)
+    got = host(engine.sgm_refine(ta, tb, torch.from_numpy(dr).cuda(), torch.from_numpy(dc).cuda(), r, s, 0.25, 1.0, paths=8,
+                                 offset=off, subpix=True, mask=torch.from_numpy(mask).cuda(), return_score=True,
+                                 return_shift=True))
+    assert_equal(got, want, (r, s))
+
+
 # ---------------------------------------------------------------------------------------------
 # cross-checks
 # ---------------------------------------------------------------------------------------------

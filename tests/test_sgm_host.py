@@ -545,10 +545,10 @@ def test_sgm_keyword():
     kw = dict(image_size=[16, 16], stride=[12, 16], degree_map_mode=list(PMODES))
     s = ImageCutSolver(a, b, sgm=SGM, **kw)
     assert s.sgm == (2, 2, 2048, 8192, 8) and s.sgm_where == 'all' and s.sgm_score_map is None and s.sgm_shift_map is None
-    assert s._sgm_keyword() == (2, 2, 2.0, 8.0, 8) and engine.sgm_params(s._sgm_keyword()) == s.sgm
+    assert s._sgm_given == SGM and engine.sgm_params(s._sgm_given) == s.sgm      # what the shard path is handed
     assert ImageCutSolver(a, b, sgm=(3, 1, 0.5, 0.5, 4), sgm_where='filled', fill=4, **kw).sgm == (3, 1, 512, 512, 4)
     s = ImageCutSolver(a, b, **kw)
-    assert s.sgm is None and s.sgm_score_map is None and s.sgm_shift_map is None and s._sgm_keyword() is None
+    assert s.sgm is None and s.sgm_score_map is None and s.sgm_shift_map is None and s._sgm_given is None
     assert 'sgm_score_map' in ImageCutSolver._MAPS and ImageCutSolver._MAPS['sgm_shift_map'] == ('sgm_shift', False)
     with pytest.raises(ValueError):
         ImageCutSolver(a, b, sgm=SGM, **dict(kw, degree_map_mode=['elevation', 'elevation2', 'distance']))

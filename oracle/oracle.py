@@ -289,7 +289,13 @@ def match_from(levels, bottom, sub_pix=True, filtering=False, filter_window_size
 
 
 def _near(M, pd0, pd1):
+    """Matching._calc_near_match (:58-78) at the centre (pd0, pd1).  A centre outside the map
+    raises: the reference raises there too (an empty window's argmax), the kernels read zeros,
+    and numpy's wrap of a negative index is what neither does.  No descent gets there -- a
+    _filter pass cannot carry a position out of its map (tests/test_filter_lattice.py)."""
     h, w = M.shape
+    if not (0 <= pd0 < h and 0 <= pd1 < w):
+        raise IndexError('position (%d, %d) outside the %d x %d map' % (pd0, pd1, h, w))
     win = np.zeros((3, 3))
     for a in range(3):
         for b in range(3):

@@ -28,18 +28,6 @@ __constant__ double c_powf_c[DM_POWF_NT] = DM_POWF_C_INIT;
 __constant__ double c_powf_p[DM_POWF_NT * 2] = DM_POWF_P_INIT;
 __constant__ double c_powf_g[(1 - DM_POWF_EMIN) * 2] = DM_POWF_G_INIT;
 
-// Kernels of a pair's tail (stats, levels >= 3, matching, sub-pixel, stitch) run beside the next
-// pair's level kernel, whose waves are older and win the SIMD's age-ordered issue arbitration on
-// nearly every cycle; a tail wave then waits for the few idle issue slots between its loads
-// and holds its wave slot ~20x longer than alone (profiles/r03y_gaps.txt).  With
-// DM_TAIL_PRIO, tail waves raise their priority (s_setprio) so their short, latency-bound
-// instruction streams issue as soon as they are ready.
-#ifdef DM_TAIL_PRIO
-#define DM_TAIL_ENTRY() __builtin_amdgcn_s_setprio(3)
-#else
-#define DM_TAIL_ENTRY() ((void)0)
-#endif
-
 __device__ __forceinline__ double pow14(double x)
 {
     if (x >= DM_POWF_XMIN && x <= 1.0) return dm_pow14_fast(x, c_powf_c, c_powf_p, c_powf_g);
@@ -205,73 +193,6 @@ __device__ __forceinline__ double pow14_k(double x, const PowLds &t)
     return pow14_zd(x, t) + (x - x); // 0 -> +0 (zero row), NaN -> NaN
 }
 
-// The float64 pows of the pruned level kernel (round 6, k_level12_prune in dm_prune.h) without
-// the gz rows: that kernel's level-1 x buffers need the LDS the 5 KB of gz took.  The 2^(yE) row
-// of a double whose exponent E is in [-126, 0] is g32[E + 127] -- the same {G, g} constants as
-// gz[E - EMIN + 1] -- so pow14_core gives the same bits; zero reads g32[0] = {0, 0} as gz[0]; NaN
-// (and the out-of-domain s / 4 > 1 of pow14_q4) the NaN row g32[255] as gz[DM_GZ_ROWS]; the rare
-// E < -126 takes dm_pow14_fast with the constant-memory tables (the same constants and
-// operations as pow14_core: fma(M, c_i, -1), the series, fma(Phi, G, fma(Phi, q, Plo) G)), or 0
-// below 2^EMIN where gz's clamp gives 0.  So pow14_q4g == pow14_q4 and pow14_kg == pow14_k bit
-// for bit on EVERY double (tests/test_pow_gpu.py through dm_pow14_variant).  T: any table
-// struct with fp, g32, fc32 (PowLds, PowLdsG).
-template <typename T>
-__device__ __forceinline__ double pow14_q4g(double s, const T &t)
-{
-    const uint64_t b = dm_bits_f64(s);
-    const unsigned hi = (unsigned)(b >> 32);
-    const double M = dm_f64_bits((b & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
-    const int i = (int)((hi >> 11) & (DM_POWF_NT - 1));
-    const int be = (int)((hi >> 20) & 0x7FF);
-    int row = be - 898;                       // E(s / 4) + 127 = be - 1025 + 127
-    if (be != 0 && row < 1) [[unlikely]] {    // s / 4 < 2^-126 (and not 0)
-        if (be - 1025 < DM_POWF_EMIN) return 0.0;
-        return dm_pow14_fast(ldexp(s, -2), c_powf_c, c_powf_p, c_powf_g);
-    }
-    row = be == 0 ? 0 : (row > 127 ? 255 : row);
-    return pow14_core_r(fma(M, (double)t.fc32[i], -1.0), i, t.g32[row], t);
-}
-
-template <typename T>
-__device__ __forceinline__ double pow14_kg(double x, const T &t)
-{
-    const uint64_t b = dm_bits_f64(x);
-    const unsigned hi = (unsigned)(b >> 32);
-    const double M = dm_f64_bits((b & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull);
-    const int i = (int)((hi >> 11) & (DM_POWF_NT - 1));
-    const int be = (int)((hi >> 20) & 0x7FF);
-    int row = be - 896;                       // E + 127
-    if (be != 0 && row < 1) [[unlikely]] {    // x < 2^-126 (and not 0)
-        if (be - 1023 < DM_POWF_EMIN) return 0.0 + (x - x);
-        return dm_pow14_fast(x, c_powf_c, c_powf_p, c_powf_g) + (x - x);
-    }
-    row = be == 0 ? 0 : (row > 127 ? 127 : row);   // (pow14_zd's clamp: x > 1 reads the E = 0 row)
-    return pow14_core_r(fma(M, (double)t.fc32[i], -1.0), i, t.g32[row], t) + (x - x);
-}
-
-// the pow tables without gz (k_level12_prune): fp, g32 (rows 128..254 a hole the kernel uses for
-// its exchange arrays), fc32
-struct PowLdsG {
-    dm_d2 fp[DM_POWF_NT];
-    dm_d2 g32[256];
-    float fc32[DM_POWF_NT];
-};
-
-__device__ __forceinline__ void pow_lds_fill_g(PowLdsG &t, int tid, int nthreads)
-{
-    for (int i = tid; i < DM_POWF_NT; i += nthreads) {
-        t.fc32[i] = (float)c_powf_c[i];
-        t.fp[i] = dm_d2{c_powf_p[2 * i], c_powf_p[2 * i + 1]};
-    }
-    for (int b = tid; b < 256; b += nthreads) {
-        if (b >= 128 && b < 255) continue;
-        const int e = b - 127 - DM_POWF_EMIN;
-        const bool in = b >= 1 && b <= 127 && e >= 0;
-        t.g32[b] = in ? dm_d2{c_powf_g[2 * e], c_powf_g[2 * e + 1]}
-                   : b == 255 ? dm_d2{(double)NAN, (double)NAN} : dm_d2{0.0, 0.0};
-    }
-}
-
 // ------------------------------------------------------------------------------------
 // geometry + workspace views
 // ------------------------------------------------------------------------------------
@@ -347,7 +268,6 @@ __device__ __forceinline__ float r_of_y_fast(float y, float a, int method)
 // ------------------------------------------------------------------------------------
 __global__ void k_stats(Geo g, Stats s)
 {
-    DM_TAIL_ENTRY();
     const int P = g.h0 * g.w0;
     const int t = blockIdx.y;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -429,7 +349,6 @@ __device__ double l1_value(const Geo &g, const Stats &s, int t, int I, int J, in
 
 #include "dm_mfma.h"
 #include "dm_strip.h"
-#include "dm_prune.h"
 
 // ------------------------------------------------------------------------------------
 // K2 (generic): one workgroup per level-1 cell (= 2x2 block of patches p).  For each
@@ -598,8 +517,6 @@ __global__ __launch_bounds__(256) void k_pow_variant(const double *in, size_t n,
         if constexpr (V == DM_POW_F32) r = pow14_zf((float)x, plds, mant);
         else if constexpr (V == DM_POW_Q4) r = pow14_q4(x, plds);
         else if constexpr (V == DM_POW_K) r = pow14_k(x, plds);
-        else if constexpr (V == DM_POW_Q4G) r = pow14_q4g(x, plds);
-        else if constexpr (V == DM_POW_KG) r = pow14_kg(x, plds);
         else r = pow14_lds(x, plds);
         out[i] = r;
     }
@@ -637,7 +554,6 @@ __device__ __forceinline__ void aggregate_at(const double *in, int h, int w, int
 
 __global__ void k_aggregate(const double *in, int T, int h, int w, int rectify, double *out)
 {
-    DM_TAIL_ENTRY();
     const size_t P2 = (size_t)(h / 2) * (w / 2);
     const size_t total = (size_t)T * P2 * P2;
     for (size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x; idx < total;
@@ -657,7 +573,6 @@ template <bool VEC>
 __global__ __launch_bounds__(256) void k_aggregate_rows(const double *in, int T, int h, int w, int BR, int rectify,
                                                         double *out)
 {
-    DM_TAIL_ENTRY();
     extern __shared__ double pooled[]; // [child][band row][v]: 4 * BR * W2 doubles (dynamic, so
                                        // small bands do not cap the workgroups per CU)
     const int h2 = h / 2, W2 = w / 2;
@@ -767,7 +682,6 @@ __device__ __forceinline__ void match_top_at(const double *LK, int h, int w, siz
 
 __global__ void k_match_top(const double *LK, int T, int h, int w, double *map)
 {
-    DM_TAIL_ENTRY();
     const size_t P = (size_t)h * w;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * P) return;
@@ -812,7 +726,6 @@ __device__ __forceinline__ void match_step_at(const Geo &g, const Stats &s, cons
 __global__ void k_match_step(Geo g, Stats s, const double *L, int lev, int T, int h, int w,
                              const double *pmap, double *cmap)
 {
-    DM_TAIL_ENTRY();
     const size_t Pn = (size_t)(2 * h) * (2 * w);
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * Pn) return;
@@ -1071,7 +984,6 @@ __device__ __forceinline__ void match_step_l1_at(const Geo &g, const Stats &s, i
 template <int WS, int MW = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MW))) void k_match_step_l1(Geo g, Stats s, int T, const double *pmap, double *cmap)
 {
-    DM_TAIL_ENTRY();
     const size_t P1 = (size_t)(g.h0 / 2) * (g.w0 / 2);
     const size_t gid = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t e = gid >> 2;
@@ -1103,7 +1015,6 @@ __device__ __forceinline__ int py_wrap(int k, int n) { return k < 0 ? k + n : k;
 
 __global__ void k_subpix(Geo g, Stats s, const double *L0, int T, int h0, int w0, int hm, int wm, double *map)
 {
-    DM_TAIL_ENTRY();
     const size_t P = (size_t)h0 * w0, Pm = (size_t)hm * wm;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * Pm) return;
@@ -1136,7 +1047,6 @@ __global__ void k_subpix(Geo g, Stats s, const double *L0, int T, int h0, int w0
 // mean / median of the neighbouring integer displacements.  in -> out (score copied).
 __global__ void k_filter(const double *in, double *out, int T, int h, int w, int fw, int median)
 {
-    DM_TAIL_ENTRY();
     const size_t P = (size_t)h * w;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * P) return;
@@ -1179,7 +1089,6 @@ __global__ void k_filter(const double *in, double *out, int T, int h, int w, int
 
 __global__ void k_cal_map(const double *map, int T, int h, int w, int mode, double *out)
 {
-    DM_TAIL_ENTRY();
     const size_t P = (size_t)h * w;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * P) return;
@@ -1223,7 +1132,6 @@ struct Modes {
 __global__ void k_stitch(const double *match, int n0, int n1, int h0, int w0, int s0, int s1,
                          Modes modes, int nmodes, double *dmap, double *score, int Hout, int Wout)
 {
-    DM_TAIL_ENTRY();
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)Hout * Wout) return;
     const int y = (int)(idx / Wout), x = (int)(idx % Wout);
@@ -1288,28 +1196,52 @@ static inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 static size_t base_stats_bytes(const dm_tiles *b) { return (size_t)6 * 4 * (size_t)b->T * b->h0 * b->w0; }
 
-// level-1 kernel variant, a function of the tile shape only (no environment, no state): 3 =
-// the column-split MFMA kernel k_level1_mfq where the shape allows it, 0 = the generic kernel.
-// dm_corr_stats lays the window operands out for the variant, and every later call on the same
-// batch re-derives the same decision from the same dm_tiles.
-static int level1_variant(const dm_tiles *b)
+// the row-pair strips (k_prep_strips): ws <= 5 on the widths that split into 1, 2 or 4 column
+// groups of 64 windows (w0 = 64, 128, 256: every wave sweeps 64 windows = 2 strip tiles per row
+// pair).  Sizes the workspace, feeds the level kernels of these shapes and the standalone volume
+// kernels' min/max sweep: a function of the shape only, no environment knobs.
+static bool strip_shape(const dm_tiles *b)
 {
-    return mf16_eligible(b) ? 3 : 0;
+    if (!mf16_eligible(b) || b->ws > 5) return false;
+    const int G = b->w0 / 16;
+    return G % 4 == 0 && (G / 4 == 1 || G / 4 == 2 || G / 4 == 4);
 }
 
-// waves per workgroup of k_level1_mfq (and the window layout dm_corr_stats writes for it):
-// column group width GW = G/NW tiles of 16 windows per wave.  GW = 4 (two pooled columns per
-// lane: the left neighbour of the second is in the lane, level 2 pools in the lane) where the
-// width gives 1, 2 or 4 such waves and the packed-y path applies (one wave: two cell blocks per
-// workgroup, launch_mfq_t); GW = 2 otherwise.  Same box,
+// THE decision which level kernel a batch runs, a function of the tile shape only (no
+// environment, no state): dm_corr_stats lays out the window operands its kernel reads, and every
+// later call on the same batch re-derives the same decision from the same dm_tiles.
+//   LK_GENERIC  k_level1_generic (dm_corr_level1 only; no MFMA operands in the workspace)
+//   LK_MFQ      k_level1_mfq, GW = 2: both sweeps on the 16 x 16 i8 tiles (k_prep_windows16)
+//   LK_MFQ_F16  k_level1_mfq, GW = 4, F16 (w0 = 128, C3): sweep 1 on the strips, sweep 2 takes num
+//               whole from the f16 MFMA (num_tile_f16; k_prep_windows16<WSC, true> writes the
+//               binary16 operands and the b_q plane, which nothing else reads: the volume kernels
+//               prep their own region)
+//   LK_STRIP    k_level12_strip (w0 = 64 and 256, C2 and C5): both sweeps on the strips; the
+//               16 x 16 window operands are not written, nothing reads them there
+// Same box, bit-identical (profiles/r05_strip_ab.txt): C5 27.06 / 27.04 ms on the strip kernel
+// against 27.44 / 27.30, C2 0.498 against 0.504 ms (mean of 4), C3 7.30 / 7.32 against 7.19 /
+// 7.18 -- there k_level1_mfq stays (the strip kernel issues 3.6 % more VALU instructions and 29 %
+// more LDS ones per launch: its lane holds two cells' normalisation constants and carries two
+// windows' odd rows; fewer MFMA cycles do not make up for it at 4 waves per SIMD).
+enum LevelKernel { LK_GENERIC, LK_MFQ, LK_MFQ_F16, LK_STRIP };
+static LevelKernel level_kernel(const dm_tiles *b)
+{
+    if (!mf16_eligible(b)) return LK_GENERIC;
+    if (!strip_shape(b)) return LK_MFQ;
+    return b->w0 == 128 ? LK_MFQ_F16 : LK_STRIP;
+}
+
+// waves per cell block of the level kernels (and the window layout dm_corr_stats writes for
+// k_level1_mfq): column group width GW = G/NW tiles of 16 windows per wave.  GW = 4 (two pooled
+// columns per lane: the left neighbour of the second is in the lane, level 2 pools in the lane)
+// on the strip shapes; GW = 2 otherwise.  Same box,
 // bit-identical (tools/kbench.py, profiles/r03k_*): C3 (S=128) 7.96 -> 7.72 ms with 2 waves of
 // GW = 4 instead of 4 waves of GW = 2 (137 VGPRs: 3 waves/SIMD instead of 5), C5 (S=256)
 // 549 -> 487 ms with 4 waves instead of 8.
 static int mfq_nw(const dm_tiles *b)
 {
     const int G = b->w0 / 16;
-    const bool g4 = b->ws * b->ws <= 25 && G % 4 == 0 && (G / 4 == 1 || G / 4 == 2 || G / 4 == 4);
-    if (g4) return G / 4;
+    if (strip_shape(b)) return G / 4;
     return G / 2 < 8 ? G / 2 : 8;
 }
 
@@ -1318,50 +1250,6 @@ static int mfq_nw(const dm_tiles *b)
 static bool volume_ls_shape(const dm_tiles *b)   // sizes the workspace: no environment knobs
 {
     return mf16_eligible(b) && b->ws <= 5 && (b->h0 % 4) == 0 && ((size_t)(b->h0 / 4) * (b->w0 / 4)) % 8 == 0;
-}
-
-
-// the row-pair strips of sweep 1 (k_prep_strips): the three GW = 4 instances of the level kernel
-// (packed y, ws <= 5; every wave sweeps 64 windows = 2 strip tiles per row pair)
-#ifndef DM_S1
-#define DM_S1 1   // 0: sweep 1 on the 16 x 16 tiles (A/B build switch)
-#endif
-static bool strip_shape(const dm_tiles *b)   // sizes the workspace: no environment knobs
-{
-    if (!DM_S1 || !mf16_eligible(b) || b->ws > 5) return false;
-    const int G = b->w0 / 16;
-    return G % 4 == 0 && (G / 4 == 1 || G / 4 == 2 || G / 4 == 4);
-}
-
-// both sweeps on the strips (k_level12_strip, dm_strip.h) for the strip shapes whose bit is set
-// in DM_S2 (1: w0 = 64, C2; 2: w0 = 128, C3; 4: w0 = 256, C5); dm_corr_stats then skips the
-// 16 x 16 window operands (k_prep_windows16), which nothing else reads there.  Same box, bit-
-// identical (profiles/r05_strip_ab.txt): C5 27.06 / 27.04 ms against 27.44 / 27.30, C2 0.498
-// against 0.504 ms (mean of 4), C3 7.30 / 7.32 against 7.19 / 7.18 -- there k_level1_mfq stays
-// (the strip kernel issues 3.6 % more VALU instructions and 29 % more LDS ones per launch: its
-// lane holds two cells' normalisation constants and carries two windows' odd rows; fewer MFMA
-// cycles do not make up for it at 4 waves per SIMD, and at 3 the lost occupancy costs more)
-#ifndef DM_S2
-#define DM_S2 5
-#endif
-static bool strip2_shape(const dm_tiles *b)
-{
-    return strip_shape(b) && ((DM_S2 >> (b->w0 == 64 ? 0 : b->w0 == 128 ? 1 : 2)) & 1);
-}
-
-// num whole from the f16 MFMA in sweep 2 (dm_mfma.h, num_tile_f16): the w0 = 128 instance of
-// k_level1_mfq (C3).  THE predicate for the window-operand layout of a batch: dm_corr_stats
-// writes the binary16 operands and the b_q plane where it holds (k_prep_windows16<WSC, true>),
-// launch_mfq_t launches the F16 instance where it holds, and nothing else reads region 1 of
-// such a batch (the volume kernels prep their own region, the pruned kernel is excluded).  The
-// workspace size is the same under both layouts (the b_q plane is half the QS region), so
-// dm_stats_bytes does not ask.
-#ifndef DM_F16Y
-#define DM_F16Y 1   // 0: the i8 tiles and the three-step y (A/B build switch)
-#endif
-static bool f16y_shape(const dm_tiles *b)
-{
-    return DM_F16Y && !DM_PRUNE && strip_shape(b) && !strip2_shape(b) && b->w0 == 128;
 }
 
 static size_t strip_bytes(const dm_tiles *b)
@@ -1451,7 +1339,6 @@ __device__ __forceinline__ void match_step_l0_at(const Geo &g, const Stats &s, i
 template <int WS, int MW = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MW))) void k_match_step_l0(Geo g, Stats s, int T, const double *pmap, double *cmap)
 {
-    DM_TAIL_ENTRY();
     const size_t Pn = (size_t)g.h0 * g.w0;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * Pn) return;
@@ -1507,7 +1394,6 @@ __device__ __forceinline__ void subpix_at(const Geo &g, const Stats &s, int t, i
 template <int WS, int MW = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MW))) void k_subpix_t(Geo g, Stats s, int T, double *map)
 {
-    DM_TAIL_ENTRY();
     const size_t P = (size_t)g.h0 * g.w0;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (idx >= (size_t)T * P) return;
@@ -1536,107 +1422,58 @@ static int launch_level1(const dm_tiles *b, Stats s, double *L1, hipStream_t st)
 #ifndef DM_C3_MINW
 #define DM_C3_MINW 4   // waves per SIMD k_level1_mfq's S = 128 instance is compiled for
 #endif
-#ifndef DM_C3_MW
-#define DM_C3_MW 4   // waves per SIMD the S = 128 strip kernel is compiled for
-#endif
 #ifndef DM_C3_NB
 #define DM_C3_NB 2   // two-wave cell blocks per workgroup of the S = 128 level kernel
 #endif
 #ifndef DM_C2_NB
 #define DM_C2_NB 4   // one-wave cell blocks per workgroup of the S = 64 level kernel
 #endif
-// the C3 level kernel with pruned child pows when DM_PRUNE is set (dm_prune.h) -> launched?
-template <bool OK>
-static bool prune_c3(const Geo &gg, const Stats &s, double *L1, double *L2, const dm_v4i *Bw, const int2 *QS,
-                     const dm_v4i *Bs, const dm_v4i *Ss, unsigned grid, hipStream_t st)
-{
-    if constexpr (DM_PRUNE && OK) {
-        if (Bs && L1 == nullptr && L2 != nullptr) {
-            k_level12_prune<2, DM_C3_NB, DM_C3_MINW><<<grid, 64 * 2 * DM_C3_NB, 0, st>>>(gg, s, L2, Bw, QS, Bs, Ss);
-            return true;
-        }
-    }
-    (void)gg; (void)s; (void)L1; (void)L2; (void)Bw; (void)QS; (void)Bs; (void)Ss; (void)grid; (void)st;
-    return false;
-}
 
-template <bool L2F, bool YF>
-static int launch_mfq_t(const dm_tiles *b, Stats s, const dm_v4i *Bw, const int2 *QS, double *L1, double *L2,
-                        hipStream_t st, const dm_v4i *Bs, const dm_v4i *Ss)
-{
-    const int KS = (b->ws * b->ws + 63) / 64, NW = mfq_nw(b), GW = b->w0 / 16 / NW;
-    const unsigned grid = (unsigned)(b->T * (b->h0 / 4) * (b->w0 / 4));
-    const Geo gg = make_geo(b);
-    // the fused path (L2F) normalises with the clamp bit of the Markstein step (norm_clamp in
-    // dm_mfma.h); the level-1-only path keeps the v_med3_f32 form
-    constexpr bool CL = L2F;
-    // GW = 4 with 4 waves (S = 256, C5): 4 waves/SIMD register budget
-    if (KS == 1 && GW == 4 && NW == 4) {
-        constexpr int NBc = DM_C5_NB;
-        const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
-        if (Bs && (DM_S2 & 4)) k_level12_strip<4, NBc, L2F, CL, 4><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
-        else if (Bs) k_level1_mfq<1, 4, 4 * NBc, 4, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
-        else k_level1_mfq<1, 4, 4 * NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        DM_HIP_TRY(hipGetLastError());
-        return DM_OK;
-    }
-    // GW = 4 with one wave per cell block (S = 64, C2): C2_NB cell blocks per workgroup share
-    // the pow tables (one-wave workgroups would hold 20 KB of LDS per wave: 2 waves/SIMD).
-    // 4 blocks: C2 level kernel 0.540 -> 0.503-0.509 ms against 2 (same box,
-    // profiles/r04g_c2nb4.txt): half the table fills and workgroup starts per wave
-    if (KS == 1 && GW == 4 && NW == 1) {
-        constexpr int NBc = DM_C2_NB;
-        const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
-        if (Bs && (DM_S2 & 1)) k_level12_strip<1, NBc, L2F, CL, 4><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
-        else if (Bs) k_level1_mfq<1, 4, NBc, 4, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
-        else k_level1_mfq<1, 4, NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        DM_HIP_TRY(hipGetLastError());
-        return DM_OK;
-    }
-    // GW = 4 with 2 waves (C3): 20 KB of LDS (the exchange arrays in the pow tables' hole)
-    // allow 8 workgroups per CU, so a 4 waves/SIMD register budget (<= 128 VGPRs)
-    if (KS == 1 && GW == 4 && NW == 2) {
-        constexpr int NBc = DM_C3_NB;
-        const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
-        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
-        if (Bs && (DM_S2 & 2)) k_level12_strip<2, NBc, L2F, CL, DM_C3_MW><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
-        // level 1 not stored: the child pows pruned to the level-2 window maxima (dm_prune.h;
-        // DM_PRUNE, off: measured slower)
-        else if (prune_c3<L2F && YF>(gg, s, L1, L2, Bw, QS, Bs, Ss, grid / NBc, st)) {}
-        else if (f16y_shape(b)) {
-            if constexpr (YF) k_level1_mfq<1, 4, 2 * NBc, DM_C3_MINW, L2F, YF, NBc, CL, YF, YF><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
-        }
-        else if (Bs) k_level1_mfq<1, 4, 2 * NBc, DM_C3_MINW, L2F, YF, NBc, CL, YF><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
-        else k_level1_mfq<1, 4, 2 * NBc, 4, L2F, YF, NBc, CL><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2);
-        DM_HIP_TRY(hipGetLastError());
-        return DM_OK;
-    }
-    // GW = 2 (ws > 5, or widths without a 4-tile split): register budget 5 waves/SIMD
-#define DM_MQ(KS_, GW_, NW_) if (KS == KS_ && GW == GW_ && NW == NW_) { k_level1_mfq<KS_, GW_, NW_, 5, L2F, YF><<<grid, 64 * NW_, 0, st>>>(gg, s, Bw, QS, L1, L2); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
-    DM_MQ(1, 2, 1) DM_MQ(1, 2, 2) DM_MQ(1, 2, 4) DM_MQ(1, 2, 8)
-    if constexpr (!YF) {
-        DM_MQ(2, 2, 1) DM_MQ(2, 2, 2) DM_MQ(2, 2, 4) DM_MQ(2, 2, 8)
-        DM_MQ(3, 2, 1) DM_MQ(3, 2, 2) DM_MQ(3, 2, 4) DM_MQ(3, 2, 8)
-        DM_MQ(4, 2, 1) DM_MQ(4, 2, 2) DM_MQ(4, 2, 4) DM_MQ(4, 2, 8)
-    }
-#undef DM_MQ
-    return dm_fail(DM_ERR_UNSUPPORTED, "no column-split instance for KS=%d GW=%d NW=%d", KS, GW, NW);
-}
-
-// the packed-f32 y (YF) needs n <= 25 (see y_of_acc)
+// Launches the MFMA level kernel level_kernel(b) names (not LK_GENERIC).  Every instance of
+// k_level1_mfq and k_level12_strip in the library is one of the launches below, and each is
+// reached by an admitted shape (tests/test_profiles.py holds the library to that set):
+//   w0 = 256, ws <= 5   k_level12_strip<4, C5_NB, L2F>              4 waves per cell block (C5)
+//   w0 =  64, ws <= 5   k_level12_strip<1, C2_NB, L2F>              C2_NB one-wave blocks share the
+//                       pow tables (one-wave workgroups would hold 20 KB of LDS per wave).  4 blocks:
+//                       0.540 -> 0.503-0.509 ms against 2 (same box, profiles/r04g_c2nb4.txt)
+//   w0 = 128, ws <= 5   k_level1_mfq<1, 4, 2 C3_NB, C3_MINW, L2F, true, C3_NB, true>   (C3) 20 KB of
+//                       LDS (the exchange arrays in the pow tables' hole) allow 8 workgroups per
+//                       CU, so a 4 waves/SIMD register budget (<= 128 VGPRs)
+//   w0 =  32, ws <= 5   k_level1_mfq<1, 2, 1, 5, L2F, true>         GW = 2 with the packed-f32 y
+//   ws >= 7             k_level1_mfq<KS, 2, NW, 5, L2F, false>      KS = ceil(ws^2 / 64) = 1 .. 4,
+//                       NW = w0 / 32 = 1, 2, 4, 8; register budget 5 waves/SIMD
+// (the packed-f32 y, YF, needs n <= 25: see y_of_acc)
 template <bool L2F>
-static int launch_mfq(const dm_tiles *b, void *d_stats, double *L1, double *L2, hipStream_t st)
+static int launch_level(const dm_tiles *b, void *d_stats, double *L1, double *L2, hipStream_t st)
 {
+    const Stats s = stats_view(d_stats, b->T, b->h0 * b->w0);
+    const Geo gg = make_geo(b);
+    const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);   // cell blocks per tile
+    const unsigned grid = (unsigned)(b->T * bpt);
+    const LevelKernel lk = level_kernel(b);
     dm_v4i *Bw;
     int2 *QS;
     mfma_views(b, d_stats, &Bw, &QS);
-    const Stats s = stats_view(d_stats, b->T, b->h0 * b->w0);
-    dm_v4i *Bs = nullptr, *Ss = nullptr;
-    if (strip_shape(b)) strip_views(b, d_stats, &Bs, &Ss);
-    if (b->ws <= 5) return launch_mfq_t<L2F, true>(b, s, Bw, QS, L1, L2, st, Bs, Ss);
-    return launch_mfq_t<L2F, false>(b, s, Bw, QS, L1, L2, st, nullptr, nullptr);
+    if (lk != LK_MFQ) {
+        dm_v4i *Bs, *Ss;
+        strip_views(b, d_stats, &Bs, &Ss);
+        const int NBc = b->w0 == 256 ? DM_C5_NB : b->w0 == 128 ? DM_C3_NB : DM_C2_NB;
+        if (bpt % NBc) return dm_fail(DM_ERR_UNSUPPORTED, "cell blocks per tile not a multiple of %d (fill_ptab: a workgroup in one tile)", NBc);
+        if (b->w0 == 256) k_level12_strip<4, DM_C5_NB, L2F><<<grid / NBc, 64 * 4 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
+        else if (b->w0 == 64) k_level12_strip<1, DM_C2_NB, L2F><<<grid / NBc, 64 * NBc, 0, st>>>(gg, s, L1, L2, Bs, Ss);
+        else k_level1_mfq<1, 4, 2 * DM_C3_NB, DM_C3_MINW, L2F, true, DM_C3_NB, true><<<grid / NBc, 64 * 2 * NBc, 0, st>>>(gg, s, Bw, QS, L1, L2, Bs, Ss);
+        DM_HIP_TRY(hipGetLastError());
+        return DM_OK;
+    }
+    const int KS = (b->ws * b->ws + 63) / 64, NW = mfq_nw(b);
+#define DM_MQ(KS_, NW_, YF_) if (KS == KS_ && NW == NW_ && (b->ws <= 5) == YF_) { k_level1_mfq<KS_, 2, NW_, 5, L2F, YF_><<<grid, 64 * NW_, 0, st>>>(gg, s, Bw, QS, L1, L2); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
+    DM_MQ(1, 1, true)
+    DM_MQ(1, 1, false) DM_MQ(1, 2, false) DM_MQ(1, 4, false) DM_MQ(1, 8, false)
+    DM_MQ(2, 1, false) DM_MQ(2, 2, false) DM_MQ(2, 4, false) DM_MQ(2, 8, false)
+    DM_MQ(3, 1, false) DM_MQ(3, 2, false) DM_MQ(3, 4, false) DM_MQ(3, 8, false)
+    DM_MQ(4, 1, false) DM_MQ(4, 2, false) DM_MQ(4, 4, false) DM_MQ(4, 8, false)
+#undef DM_MQ
+    return dm_fail(DM_ERR_UNSUPPORTED, "no column-split instance for KS=%d NW=%d ws=%d", KS, NW, b->ws);
 }
 
 // LDS-shared-window volume kernel (k_volume_ls): ws <= 5 on the MFMA shapes, 8 waves (patch
@@ -1692,18 +1529,15 @@ static int launch_mfq(const dm_tiles *b, void *d_stats, double *L1, double *L2, 
 #ifndef DM_VL_F_NT
 #define DM_VL_F_NT 1
 #endif
-// the min/max sweep of the volume kernels without a known min/max on the row-pair strips
-// dm_corr_stats leaves for the strip shapes (32 x 32 x 32 i8 MFMA, as the level kernel's sweep 1)
-#ifndef DM_VS1
-#define DM_VS1 1
-#endif
+// (the min/max sweep of the volume kernels without a known min/max runs on the row-pair strips
+// dm_corr_stats leaves for the strip shapes: 32 x 32 x 32 i8 MFMA, as the level kernel's sweep 1)
 template <typename OT>
 static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT *out, hipStream_t st,
                             int have_mm = 0)
 {
     if (!volume_ls_shape(b)) return DM_ERR_UNSUPPORTED;
     dm_v4i *Bs = nullptr, *Ss = nullptr;
-    if (DM_VS1 && !have_mm && strip_shape(b)) strip_views(b, d_stats, &Bs, &Ss);
+    if (!have_mm && strip_shape(b)) strip_views(b, d_stats, &Bs, &Ss);
     const int G = b->w0 / 16, nw = 8;
     const size_t bpt = (size_t)(b->h0 / 4) * (b->w0 / 4);
     if (bpt % nw) return DM_ERR_UNSUPPORTED;
@@ -1761,7 +1595,8 @@ static int launch_volume_ls(const dm_tiles *b, void *d_stats, const Stats &s, OT
         }
     }
 #define DM_VL(G_) if (G == G_) { k_volume_ls<G_, 8, true, OT><<<grid, 64 * 8, 0, st>>>(gg, s, Bw, QS, out, have_mm, Bs, Ss); DM_HIP_TRY(hipGetLastError()); return DM_OK; }
-    DM_VL(2) DM_VL(4) DM_VL(8) DM_VL(16)
+    DM_VL(2) DM_VL(4)
+    if constexpr (sizeof(OT) == 2) { DM_VL(8) DM_VL(16) }   // (float32 at these widths: launched above)
 #undef DM_VL
     return DM_ERR_UNSUPPORTED;
 }
@@ -1794,7 +1629,7 @@ int dm_abi_version(void) { return 110; }
 #define DM_STR(x) DM_STR2(x)
 const char *dm_build_config(void)
 {
-    return "S1=" DM_STR(DM_S1) " F16Y=" DM_STR(DM_F16Y) " S2=" DM_STR(DM_S2) " PRUNE=" DM_STR(DM_PRUNE) " STRIP_WAVESYNC=" DM_STR(DM_STRIP_WAVESYNC) " VS1=" DM_STR(DM_VS1) " VS1_LDS=" DM_STR(DM_VS1_LDS) " XCD_MAP=" DM_STR(DM_XCD_MAP) " C2_NB=" DM_STR(DM_C2_NB) " C3_NB=" DM_STR(DM_C3_NB) " C3_MW=" DM_STR(DM_C3_MW) " C3_MINW=" DM_STR(DM_C3_MINW) " C5_NB=" DM_STR(DM_C5_NB)
+    return "C2_NB=" DM_STR(DM_C2_NB) " C3_NB=" DM_STR(DM_C3_NB) " C3_MINW=" DM_STR(DM_C3_MINW) " C5_NB=" DM_STR(DM_C5_NB)
            " VL_H_TR=" DM_STR(DM_VL_H_TR) " VL_H_NT=" DM_STR(DM_VL_H_NT) " VL_H_NW=" DM_STR(DM_VL_H_NW)
            " VL_H2_TR=" DM_STR(DM_VL_H2_TR) " VL_H2_NW=" DM_STR(DM_VL_H2_NW) " VL_F2_TR=" DM_STR(DM_VL_F2_TR)
            " VL_F2_MW=" DM_STR(DM_VL_F2_MW) " VL_HS_NW=" DM_STR(DM_VL_HS_NW) " VL_HS_TR=" DM_STR(DM_VL_HS_TR) " VL_F_NW=" DM_STR(DM_VL_F_NW)
@@ -1818,7 +1653,7 @@ size_t dm_stats_bytes(const dm_tiles *b)
 {
     if (!b) return 0;
     size_t n = base_stats_bytes(b), extra = 0;
-    if (b->ws >= 1 && b->ws <= 15 && b->T > 0 && b->h0 > 0 && b->w0 > 0 && mf16_eligible(b))
+    if (b->ws >= 1 && b->ws <= 15 && b->T > 0 && b->h0 > 0 && b->w0 > 0 && level_kernel(b) != LK_GENERIC)
         extra = mf16_extra_bytes(b);
     if (!extra) return n;
     size_t tot = align256(n) + align256(extra);
@@ -1830,7 +1665,7 @@ size_t dm_stats_bytes(const dm_tiles *b)
 int dm_level_num_f16(const dm_tiles *b)
 {
     if (!b || b->ws < 1 || b->ws > 15 || b->T <= 0 || b->h0 <= 0 || b->w0 <= 0) return 0;
-    return f16y_shape(b) ? 1 : 0;
+    return level_kernel(b) == LK_MFQ_F16 ? 1 : 0;
 }
 
 int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
@@ -1842,19 +1677,19 @@ int dm_corr_stats(const dm_tiles *b, void *d_stats, void *stream)
     dim3 grid(nblk(P, 256), b->T);
     k_stats<<<grid, 256, 0, (hipStream_t)stream>>>(make_geo(b), stats_view(d_stats, b->T, P));
     DM_HIP_TRY(hipGetLastError());
-    const int var = level1_variant(b);
-    if (var) { // MFMA-B-ordered windows + packed per-window stats for dm_corr_level1
+    const LevelKernel lk = level_kernel(b);
+    if (lk != LK_GENERIC) { // the window operands of the level kernel lk (and of the volume kernels)
         dm_v4i *Bw;
         int2 *QS;
         mfma_views(b, d_stats, &Bw, &QS);
         const int G = b->w0 / 16, KS = (b->ws * b->ws + 63) / 64;
         const size_t n = (size_t)b->T * b->h0 * G * 16;
         const int GW = G / mfq_nw(b);
-        if (f16y_shape(b)) {
+        if (lk == LK_MFQ_F16) {
             if (b->ws == 5) k_prep_windows16<5, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             else k_prep_windows16<0, true><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             DM_HIP_TRY(hipGetLastError());
-        } else if (!strip2_shape(b)) {
+        } else if (lk == LK_MFQ) {
             if (b->ws == 5) k_prep_windows16<5><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             else k_prep_windows16<0><<<nblk(n, 256), 256, 0, (hipStream_t)stream>>>(make_geo(b), G, GW, KS, Bw, QS);
             DM_HIP_TRY(hipGetLastError());
@@ -1881,8 +1716,7 @@ int dm_corr_level1(const dm_tiles *b, void *d_stats, double *d_level1, void *str
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     hipStream_t st = (hipStream_t)stream;
-    const int var = level1_variant(b);
-    if (var == 3) return launch_mfq<false>(b, d_stats, d_level1, nullptr, st);
+    if (level_kernel(b) != LK_GENERIC) return launch_level<false>(b, d_stats, d_level1, nullptr, st);
     if (P > DM_GENERIC_MAX_P || k2_lds_bytes(b->h0, b->w0, b->ws) > 160 * 1024)
         return dm_fail(DM_ERR_UNSUPPORTED, "tile too large for the generic level-1 kernel (P=%d)", P);
     switch (b->ws) {
@@ -1903,10 +1737,10 @@ int dm_corr_level12(const dm_tiles *b, void *d_stats, double *d_level1, double *
     int rc = check_tiles(b);
     if (rc) return rc;
     if (!d_stats || !d_level2) return dm_fail(DM_ERR_ARG, "null workspace / output");
-    if (level1_variant(b) != 3)
+    if (level_kernel(b) == LK_GENERIC)
         return dm_fail(DM_ERR_UNSUPPORTED, "fused level-1/level-2 kernel needs h0 %% 4 == 0, w0 %% 32 == 0, w0 <= 256, ws <= 15 (got %dx%d, ws %d)",
                     b->h0, b->w0, b->ws);
-    return launch_mfq<true>(b, d_stats, d_level1, d_level2, (hipStream_t)stream);
+    return launch_level<true>(b, d_stats, d_level1, d_level2, (hipStream_t)stream);
 }
 
 static int volume_f32(const dm_tiles *b, void *d_stats, float *d_l0, void *stream, int have_mm)
@@ -1919,7 +1753,7 @@ static int volume_f32(const dm_tiles *b, void *d_stats, float *d_l0, void *strea
     const int P = b->h0 * b->w0;
     Stats s = stats_view(d_stats, b->T, P);
     dim3 grid(P, b->T);
-    if (level1_variant(b) == 3) { // MFMA paths (the window layouts of dm_corr_stats / k_volume_ls)
+    if (level_kernel(b) != LK_GENERIC) { // MFMA paths (the window layouts of dm_corr_stats / k_volume_ls)
         rc = launch_volume_ls<float>(b, d_stats, s, d_l0, (hipStream_t)stream, have_mm);
         if (rc != DM_ERR_UNSUPPORTED) return rc;
         rc = launch_volume_mfq<float>(b, d_stats, s, d_l0, (hipStream_t)stream);
@@ -1943,7 +1777,7 @@ static int volume_f16(const dm_tiles *b, void *d_stats, uint16_t *d_l0, void *st
     Stats s = stats_view(d_stats, b->T, P);
     _Float16 *out = (_Float16 *)d_l0;
     hipStream_t st = (hipStream_t)stream;
-    if (level1_variant(b) == 3) {
+    if (level_kernel(b) != LK_GENERIC) {
         rc = launch_volume_ls<_Float16>(b, d_stats, s, out, st, have_mm);
         if (rc != DM_ERR_UNSUPPORTED) return rc;
         rc = launch_volume_mfq<_Float16>(b, d_stats, s, out, st);
@@ -2004,8 +1838,6 @@ int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_ou
     case DM_POW_F32: k_pow_variant<DM_POW_F32><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     case DM_POW_Q4: k_pow_variant<DM_POW_Q4><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     case DM_POW_K: k_pow_variant<DM_POW_K><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
-    case DM_POW_Q4G: k_pow_variant<DM_POW_Q4G><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
-    case DM_POW_KG: k_pow_variant<DM_POW_KG><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     case DM_POW_FULL: k_pow_variant<DM_POW_FULL><<<grid, 256, 0, st>>>(d_in, n, d_out); break;
     default: return dm_fail(DM_ERR_ARG, "unknown pow14 variant %d", variant);
     }

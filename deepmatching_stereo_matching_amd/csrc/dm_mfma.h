@@ -16,18 +16,6 @@
 typedef int dm_v4i __attribute__((ext_vector_type(4)));
 typedef int dm_v2i __attribute__((ext_vector_type(2)));
 
-// ABLATION ONLY (tools/abl_build.sh f16y; results WRONG): the price of taking num from the
-// f16 MFMA (num_tile_f16 below) in sweep 2 before that is built -- sweep 2 of the strip-sweep
-// instances of k_level1_mfq feeds today's i8 fragments to v_mfma_f32_16x16x32_f16 and takes y
-// as the one packed multiply D * b_q.  Bit 14 of every binary16 half of the operands is
-// cleared (the patch operand in the kernel, once per wave; the window operands where
-// k_prep_windows16 writes them) so that none is an infinity or a NaN: the values are
-// meaningless but finite, and the kernel's instruction stream is the one being priced.
-#ifndef DM_ABL_F16Y
-#define DM_ABL_F16Y 0
-#endif
-#define DM_ABL_F16_FINITE ((int)0xBFFFBFFF)
-
 // ===================================================================================
 // num = n sum_k T'_k I'_k - sT sI as ONE v_mfma_f32_16x16x32_f16 (ws <= 5), exact.
 // The i8 MFMA returns the dot product only, and y_of_acc spends two packed-f32 steps per
@@ -129,7 +117,7 @@ __global__ __launch_bounds__(64) void k_debug_num_tile_f16(const uint8_t *__rest
 // k_level1_mfq; GW = 16 B of output per lane for k_volume_ls.
 // WSC: window side known at compile time (0 = g.ws): the window's bytes are loaded once and
 // serve both the sums and the fragments.
-// F16 (f16y_shape: KS == 1, ws <= 5, GW == 4): the same Bw indexing, but all 16 bytes of a lane
+// F16 (level_kernel == LK_MFQ_F16: KS == 1, ws <= 5, GW == 4): the same Bw indexing, but all 16 bytes of a lane
 // are K data -- the binary16 window operand of num_tile_f16, slots 8 hq .. 8 hq + 7 (ws * I' in
 // slots 0 .. n-1, the negated digits of sum(I') in n .. n+3) -- and the QS region holds b_q
 // alone as a float32 plane [t][q0][q1]: lane c's four tiles of column group w are windows
@@ -137,7 +125,6 @@ __global__ __launch_bounds__(64) void k_debug_num_tile_f16(const uint8_t *__rest
 template <int WSC, bool F16 = false>
 __global__ void k_prep_windows16(Geo g, int G, int GW, int KS, dm_v4i *Bw, int2 *QS)
 {
-    DM_TAIL_ENTRY();
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const size_t total = (size_t)g.T * g.h0 * G * 16;
     if (idx >= total) return;
@@ -193,10 +180,6 @@ __global__ void k_prep_windows16(Geo g, int G, int GW, int KS, dm_v4i *Bw, int2 
                 }
                 w[2] = qx;
                 w[3] = qy;
-#if DM_ABL_F16Y
-                // ABLATION ONLY: finite binary16 halves (qx's already are: |s| < 2^12)
-                w[0] &= DM_ABL_F16_FINITE; w[1] &= DM_ABL_F16_FINITE; w[3] &= (int)0xFFFFBFFF;
-#endif
             } else {
                 for (int j = 0; j < 16; ++j) {
                     const int k = 64 * ks + 16 * hq + j;
@@ -255,7 +238,6 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const uint8_t *img, 
 template <int WSC>
 __global__ void k_prep_strips(Geo g, dm_v4i *Bs, dm_v4i *Ss)
 {
-    DM_TAIL_ENTRY();
     const int ws = WSC ? WSC : g.ws, NS = (ws + 1) * ws;
     const size_t idx = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     const int h2 = g.h0 / 2, w0 = g.w0;
@@ -292,21 +274,12 @@ __global__ void k_prep_strips(Geo g, dm_v4i *Bs, dm_v4i *Ss)
     }
 }
 
-// XCD-aware workgroup order (DM_XCD_MAP): workgroups are dealt round robin over the 8 XCDs
+// XCD-aware workgroup order (wg_logical): workgroups are dealt round robin over the 8 XCDs
 // (MI355X_MICROARCH.md, workgroup dispatch), so consecutive workgroups -- the cell blocks of one
 // tile, which read the same window operands -- land on 8 different L2s.  With the grid a
 // multiple of 8, workgroup b is given logical index (b % 8) * (grid / 8) + b / 8: each XCD then
 // walks one contiguous range of blocks, i.e. whole tiles in order, and the tile's window
 // operands stay in that XCD's L2 (placement only: any order is correct).
-#ifndef DM_LATE
-#define DM_LATE 1   // k_level1_mfq (L2F): the next even row's fragments loaded after the emission
-#endif
-#ifndef DM_XCD_MAP
-#define DM_XCD_MAP 1
-#endif
-#ifndef DM_ABL_PAPPROX
-#define DM_ABL_PAPPROX 0   // ablation builds only (tools/abl_build.sh papprox, papprox2)
-#endif
 // In-kernel clock of the level kernels (diagnostic builds only: tools/abl_build.sh clk,
 // MI355X_MICROARCH.md 'DVFS give-back' item 6): wave 0 of every workgroup reads the shader
 // clock counter and the 100 MHz real-time counter when the workgroup starts and when it
@@ -337,11 +310,11 @@ struct ClockStamp {
 __device__ __forceinline__ int wg_logical()
 {
     const int b = blockIdx.x, n = gridDim.x;
-    if (!DM_XCD_MAP || (n & 7)) return b;
+    if (n & 7) return b;
     return (b & 7) * (n >> 3) + (b >> 3);
 }
 
-// The workgroup's patch taps in LDS (S1 instances): ptab[sb][patch][0..7] = the 16 patches' taps
+// The workgroup's patch taps in LDS (the kernels with a strip sweep): ptab[sb][patch][0..7] = the 16 patches' taps
 // 0 .. 31 as int8 (zero from n on), [8..15] the same shifted by ws bytes (ws zero bytes, then
 // the taps): exactly the K bytes of the strip MFMA's A rows (offset 0 and 1), and the first copy
 // holds build_a's spread fragments (taps 8 grp .. 8 grp + 7).  One pass of the workgroup's
@@ -647,28 +620,30 @@ struct XchOwn<true, T, OFF> {
 };
 
 // L1 may be null when L2F (level 1 then lives only on chip); L2 is written when L2F.
-// NB 2x2-cell blocks per workgroup (NB = 2 where one wave spans a whole tile row, S = 64):
-// waves sb * NWc .. sb * NWc + NWc - 1 split block sb's columns; the blocks share the pow
-// tables, which is what a workgroup of more than one wave buys there.
-// S1: sweep 1 on the row-pair strips (Bs, Ss: k_prep_strips) with the 32 x 32 x 32 i8 MFMA --
-// half the matrix-core issue cycles of the 16 x 16 tiles per voxel (A rows from the LDS tap table,
-// fill_ptab), and the window stats
-// broadcast without copies; sweep 2 keeps the 16 x 16 layout its pooling needs.
-// F16 (with S1; k_prep_windows16<WSC, true> wrote Bw / QS): sweep 2 takes num whole from the f16
-// MFMA (num_tile_f16) and y = num * b_q is one packed multiply per two voxels -- no accumulator
-// bias, no patch sums in registers, b_q from the float32 plane in QS.
-template <int KS, int GW, int NW, int MINW, bool L2F, bool YF, int NB = 1, bool CL = false, bool S1 = false,
-          bool F16 = false>
+// NB 2x2-cell blocks per workgroup: waves sb * NWc .. sb * NWc + NWc - 1 split block sb's
+// columns; the blocks share the pow tables, which is what a workgroup of more than one wave
+// buys there.
+// F16 (the w0 = 128 instance, GW = 4; needs Bs, Ss, and k_prep_windows16<WSC, true> wrote Bw / QS):
+//   sweep 1 (S1) runs on the row-pair strips (Bs, Ss: k_prep_strips) with the 32 x 32 x 32 i8
+//   MFMA -- half the matrix-core issue cycles of the 16 x 16 tiles per voxel (A rows from the LDS
+//   tap table, fill_ptab), and the window stats broadcast without copies; sweep 2 keeps the
+//   16 x 16 layout its pooling needs, takes num whole from the f16 MFMA (num_tile_f16), and
+//   y = num * b_q is one packed multiply per two voxels -- no accumulator bias, no patch sums in
+//   registers, b_q from the float32 plane in QS.  Fused with level 2 (L2F) it normalises with the
+//   clamp bit of the Markstein step (CL, pk_fma_clamp01); the other instances keep v_med3_f32.
+// The other instances (GW = 2: ws > 5, or w0 = 32) run both sweeps on the 16 x 16 i8 tiles.
+template <int KS, int GW, int NW, int MINW, bool L2F, bool YF, int NB = 1, bool F16 = false>
 __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, const dm_v4i *__restrict__ Bw,
                                                         const int2 *__restrict__ QS, double *L1, double *L2,
                                                         const dm_v4i *__restrict__ Bs = nullptr,
                                                         const dm_v4i *__restrict__ Ss = nullptr)
 {
     DM_CLOCK_STAMP_HERE
-    static_assert(!F16 || (S1 && KS == 1 && GW == 4 && YF), "f16 num: strip sweep 1, one 16-byte b_q load per lane and row");
+    constexpr bool S1 = F16;          // sweep 1 on the strips: the F16 instance (the other strip shapes run k_level12_strip)
+    constexpr bool CL = F16 && L2F;   // clamp-bit normalisation (pk_fma_clamp01): the fused F16 instance
+    static_assert(!F16 || (KS == 1 && GW == 4 && YF), "f16 num: strip sweep 1, one 16-byte b_q load per lane and row");
     constexpr bool EQ = KS == 1 && YF;           // window stats ride in the B tile (qs_of_frag)
     static_assert(NW % NB == 0, "blocks split the waves evenly");
-    static_assert(!CL || L2F, "clamp-bit normalisation: NaN cells are restored at the level-2 / level-1 stores");
     constexpr int NWc = NW / NB;                 // waves per cell block
     constexpr int XS = NWc > 1 ? NWc + 1 : 1;    // exchange slots (unused with one wave per block)
     constexpr int XW = NWc > 1 ? NWc : 1;
@@ -698,7 +673,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
     __shared__ float4 cst[NB][4][6];   // [block][cell][field][child]: a_p, lo, hi, rmin, den, rinv
     // LATE: the next even row's fragments are loaded after the level-1 emission instead of
     // before it (12 fewer live VGPRs through the emission, less latency cover)
-    constexpr bool LATE = L2F && DM_LATE;
+    constexpr bool LATE = L2F;
     constexpr int L2V = 4 * GW, L2B = 64 / L2V; // level-2 values per wave per row; rows per stash
     // M == 1 (one pooled column per lane, valid on even lanes): the pooled children of RB
     // level-2 rows, [wave][row * 4 * L2V + child * L2V + column], rectified 64 at a time
@@ -748,23 +723,15 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
                 const int j = k - 8 * grp; // 0 .. 7
                 return (int)(signed char)(((unsigned)(j < 4 ? tp.x : tp.y)) >> (8 * (j & 3)));
             };
-            A[0] = f16_frag<false>(tap, s.sT[tb + pa], n, g.ws, grp);
-            return; // the patch sums are inside the product
-        }
-        if constexpr (S1) { // the spread fragment: taps 8 grp .. 8 grp + 7 of patch row c (ptab)
-            const dm_v2i tp = *(const dm_v2i *)&ptab[sb][c][2 * grp];
-            A[0] = dm_v4i{tp.x, tp.y, 0, 0};
-#if DM_ABL_F16Y
-            A[0].x &= DM_ABL_F16_FINITE; A[0].y &= DM_ABL_F16_FINITE; // ABLATION ONLY
-#endif
+            A[0] = f16_frag<false>(tap, s.sT[tb + pa], n, g.ws, grp);   // (the patch sums are inside the product)
         } else {
             build_a<KS>(A, g, t, I0, J0, c, grp);
-        }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int p = (2 * Ic + (r >> 1)) * w0 + 2 * Jc + (r & 1);
-            sTr[r] = s.sT[tb + p];
-            sTf[r] = (float)sTr[r];
+            for (int r = 0; r < 4; ++r) {
+                const int p = (2 * Ic + (r >> 1)) * w0 + 2 * Jc + (r & 1);
+                sTr[r] = s.sT[tb + p];
+                sTf[r] = (float)sTr[r];
+            }
         }
     };
     if constexpr (!S1) init_a16();
@@ -973,17 +940,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
                 const dm_f2 bb = (tw & 1) ? __builtin_shufflevector(q2, q2, 1, 1) : __builtin_shufflevector(q2, q2, 0, 0);
                 const dm_f2 y01 = dm_f2{d[0], d[1]} * bb, y23 = dm_f2{d[2], d[3]} * bb;
                 y[0] = y01.x; y[1] = y01.y; y[2] = y23.x; y[3] = y23.y;
-            } else
-#if DM_ABL_F16Y
-            if constexpr (S1 && EQ) { // ABLATION ONLY (results wrong): f16 MFMA, y = D * b_q
-                const dm_v4f d = num_tile_f16(A[0], f.b[tw][0]);
-                const dm_f2 q2 = qs_of_frag(f.b[tw][0]);
-                const dm_f2 bb = __builtin_shufflevector(q2, q2, 1, 1);   // (no asm on D: see F16 above)
-                const dm_f2 y01 = dm_f2{d[0], d[1]} * bb, y23 = dm_f2{d[2], d[3]} * bb;
-                y[0] = y01.x; y[1] = y01.y; y[2] = y23.x; y[3] = y23.y;
-            } else
-#endif
-            {
+            } else {
                 const dm_v4i acc = mfma_tile<KS, EQ>(A, f.b[tw], acc0);
                 y_of_acc<YF>(acc, sTr, sTf, EQ ? qs_of_frag(f.b[tw][0]) : qs_pair(f.q[tw]), n, y);
             }
@@ -1157,22 +1114,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void k_level1_mfq(Geo g, Stats s, co
             double sum = 0.0;
 #pragma unroll
             for (int r = 0; r < 4; ++r) { // ul, ur, ll, lr: left-to-right sum
-#if DM_ABL_PAPPROX
-                // ABLATION ONLY (tools/abl_build.sh papprox / papprox2; results WRONG): the price of
-                // pruning the child pows -- the bin-centre approximation (1/c_i)^y * 2^(yE) (two
-                // table reads and a multiply, within 0.21 % of pow14) for every child, and with
-                // DM_ABL_PAPPROX == 2 the exact pow for 2 of the lane's 8 children per row (4 per
-                // level-2 window row: one exact level-1 value per window, the ideal pruned count)
-                double pv;
-                if (DM_ABL_PAPPROX == 2 && m == 0 && r < 2) pv = pow14_zf(x[r], plds, mant);
-                else {
-                    const unsigned u = __float_as_uint(x[r]);
-                    const unsigned ofp = (u >> 10) & 0x1FF0u, og = (u >> 19) & 0xFF0u;
-                    pv = (*(const dm_d2 *)((const char *)plds.fp + ofp)).x * (*(const dm_d2 *)((const char *)plds.g32 + og)).x;
-                }
-#else
                 const double pv = pow14_zf(x[r], plds, mant);
-#endif
                 sum = r == 0 ? pv : sum + pv;
             }
             // level 1 = pow14(sum / 4), rectified where it is read: here when level 1 is
@@ -1400,14 +1342,10 @@ __global__ __launch_bounds__(256) void k_volume_mfq(Geo g, Stats s, const dm_v4i
 // or read from L2 by every wave (0).  Same box, bit-identical (profiles/r05x_vs1lds_ab.txt):
 // C3 float32 13.58/13.56 -> 12.64/12.70 ms, C5-size binary16 16.00/16.13 -> 15.78/15.79,
 // C3 binary16 and C5-size float32 within 0.4 %
-#ifndef DM_VS1_LDS
-#define DM_VS1_LDS 1
-#endif
 template <int G, int NW, bool NT, typename OT, int TR = 0, int MW = 1, int GW = (16 / (int)sizeof(OT)) < G ? (16 / (int)sizeof(OT)) : G>
 __global__ __launch_bounds__(64 * NW, MW) void k_volume_ls(Geo g, Stats s, const dm_v4i *__restrict__ Bw,
                                                    const int2 *__restrict__ QS, OT *vol, int have_mm,
-                                                   const dm_v4i *__restrict__ Bs = nullptr,
-                                                   const dm_v4i *__restrict__ Ss = nullptr)
+                                                   const dm_v4i *__restrict__ Bs, const dm_v4i *__restrict__ Ss)
 {
     // have_mm: the per-patch rmin / rmax are already in the statistics workspace (written by
     // dm_corr_level1/12 or an earlier volume launch on the same stats): sweep 1 -- the MFMA,
@@ -1490,7 +1428,7 @@ __global__ __launch_bounds__(64 * NW, MW) void k_volume_ls(Geo g, Stats s, const
         }
         clamp = __builtin_amdgcn_ballot_w64(clamp) != 0;
         asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    } else if (Bs) {
+    } else if (Bs) {   // (null where the shape has no strips: w0 = 32)
         // ---- sweep 1 on the row-pair strips (dm_corr_stats' k_prep_strips, round 5): the
         // 32 x 32 x 32 i8 MFMA gives this wave's 16 patches x 2 window rows x 32 windows per
         // instruction (k_level1_mfq's strip sweep); the strips come from memory, so the LDS
@@ -1577,7 +1515,7 @@ __global__ __launch_bounds__(64 * NW, MW) void k_volume_ls(Geo g, Stats s, const
                 }
             }
         };
-        if constexpr (DM_VS1_LDS && BUF >= 4096) {
+        if constexpr (BUF >= 4096) {
             // the workgroup's waves sweep the same units: each unit's 2 strip tiles (2 KB) and
             // window stats (1 KB) come into LDS once per workgroup by LDS-DMA (instruction i by
             // wave i % NW), double-buffered in the row buffers, one barrier per unit

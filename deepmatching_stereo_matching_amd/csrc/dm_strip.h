@@ -27,32 +27,16 @@
 // the two kernels agree bit for bit.
 #pragma once
 
-// LDS hand-over inside one cell block: a workgroup barrier when the block spans NWc > 1 waves,
-// a wave barrier (with the LDS fences) when the block is one wave
-#ifndef DM_STRIP_WAVESYNC
-#define DM_STRIP_WAVESYNC 0   // 1: wave barriers for one-wave blocks (C2) -- A/B switch, measured neutral (round 6)
-#endif
-template <int NWc>
-__device__ __forceinline__ void block_sync()
-{
-    if constexpr (NWc > 1 || !DM_STRIP_WAVESYNC) {
-        __syncthreads();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-}
-
-template <int NWc, int NB, bool L2F, bool CL, int MINW>
-__global__ __launch_bounds__(64 * NWc * NB, MINW) void k_level12_strip(Geo g, Stats s, double *L1, double *L2,
+// L2F: fused with level 2; it then normalises with the clamp bit of the Markstein step (CL,
+// pk_fma_clamp01 in dm_mfma.h).  Compiled for 4 waves per SIMD.
+template <int NWc, int NB, bool L2F>
+__global__ __launch_bounds__(64 * NWc * NB, 4) void k_level12_strip(Geo g, Stats s, double *L1, double *L2,
                                                                        const dm_v4i *__restrict__ Bs,
                                                                        const dm_v4i *__restrict__ Ss)
 {
     DM_CLOCK_STAMP_HERE
     constexpr int NW = NWc * NB;
-    constexpr bool RICH = MINW < 4;   // register budget of 3 waves / SIMD (or fewer)
-    static_assert(!CL || L2F, "clamp-bit normalisation: NaN cells are restored at the level-2 / level-1 stores");
+    constexpr bool CL = L2F;   // NaN cells are restored at the level-2 / level-1 stores
     __shared__ PowLds plds;
     // [block][pair parity][slot][16-lane row][patch slot]: the row-pooled y of window 2 c32 + 1
     // of the last lane of the 16-lane row before (slot w, rows 1 / 3: lanes 15 / 47 of wave w;
@@ -178,10 +162,9 @@ __global__ __launch_bounds__(64 * NWc * NB, MINW) void k_level12_strip(Geo g, St
     }
     StripFrag f2;
     load_strip(f2, 0); // sweep 2's first row pair, in flight through the reduction
-    // the reduction's partial extremes: from the block's waves (a workgroup barrier), or with one
-    // wave per block (NWc == 1: C2) from this wave alone -- a wave barrier, so the workgroup's
-    // NB independent blocks do not wait for each other between the sweeps (round 6)
-    block_sync<NWc>();
+    // the reduction's partial extremes from the block's waves: a workgroup barrier (with one wave
+    // per block, NWc == 1, a wave barrier would do; measured neutral at C2)
+    __syncthreads();
     // per-patch normalisation constants {a_p, lo, hi, rmin, den, RN(1/den)} -> LDS (k_level1_mfq's)
     if (wc == 0 && (lane & 15) < 4) {
         const int r = lane & 15, grp = lane >> 4;
@@ -204,7 +187,7 @@ __global__ __launch_bounds__(64 * NWc * NB, MINW) void k_level12_strip(Geo g, St
         s.rmn[tb + p] = rmn;
         s.rmx[tb + p] = rmx;
     }
-    block_sync<NWc>();
+    __syncthreads();
 
     // ---- sweep 2: pool on y -> normalise + rectify -> children sum -> level 1 [-> level 2] ----
     const bool bflat = CL && __builtin_amdgcn_readfirstlane((int)(cell_flat(cst[sb][0][4]) || cell_flat(cst[sb][1][4]) ||
@@ -289,18 +272,11 @@ __global__ __launch_bounds__(64 * NWc * NB, MINW) void k_level12_strip(Geo g, St
         const int nx = __builtin_amdgcn_readfirstlane(u + 1 < h2 ? u + 1 : u);
         const int k = u & 1;
         float rm[2][8];
-        // RICH (< 4 waves per SIMD): A and the patch sums stay in registers; otherwise they are
-        // re-read from LDS here (no registers held through the pows)
-        const dm_v4i A2 = RICH ? A32 : *A32p;
-        float sT2[8];
-        if constexpr (RICH) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) sT2[k] = sTs[k];
-        } else {
-            const float4 s0 = cst[sb][hs][6], s1 = cst[sb][2 + hs][6];
-            sT2[0] = s0.x; sT2[1] = s0.y; sT2[2] = s0.z; sT2[3] = s0.w;
-            sT2[4] = s1.x; sT2[5] = s1.y; sT2[6] = s1.z; sT2[7] = s1.w;
-        }
+        // A and the patch sums are re-read from LDS here (no registers held through the pows at
+        // the kernel's 4 waves per SIMD)
+        const dm_v4i A2 = *A32p;
+        const float4 s0 = cst[sb][hs][6], s1 = cst[sb][2 + hs][6];
+        const float sT2[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             float y[16];
@@ -388,14 +364,7 @@ __global__ __launch_bounds__(64 * NWc * NB, MINW) void k_level12_strip(Geo g, St
         }
     };
 
-    if constexpr (RICH) {
-        for (int u = 0; u < h2; u += 2) { // h2 even: the carried rows alternate registers, no copies
-            pair(f2, u);
-            pair(f2, u + 1);
-        }
-    } else {
-        for (int u = 0; u < h2; ++u) pair(f2, u);
-    }
+    for (int u = 0; u < h2; ++u) pair(f2, u);
     if constexpr (L2F) {
         const int u = h2 - 1;
         if (NWc > 1 && c32 == 31) {

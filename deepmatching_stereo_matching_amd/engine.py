@@ -524,7 +524,7 @@ def level12_fused(h0, w0, ws):
     """Does the fused level kernel (dm_corr_level12) take tiles of this shape, so that a
     DevicePyramid in mode 2 never stores level 1?  The library's own rule, restated:
     mf16_eligible (csrc/dm_mfma.h: h0 % 4 == 0, w0 a power of two in 32 .. 256, ws <= 15) and,
-    on the three GW = 4 instances (ws <= 5, w0 = 64 / 128 / 256: launch_mfq_t in
+    on the three GW = 4 instances (ws <= 5, w0 = 64 / 128 / 256: launch_level in
     csrc/dm_kernels.hip), cell blocks per tile a multiple of the NB cell blocks a workgroup
     holds -- NB read from the loaded library's build configuration, not assumed."""
     if not (h0 > 0 and h0 % 4 == 0 and w0 in (32, 64, 128, 256) and 1 <= ws <= 15 and ws % 2 == 1):

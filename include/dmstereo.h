@@ -147,10 +147,9 @@ int dm_rectify64(const double *d_in, size_t n, double *d_out, void *stream);
  *                s = +inf NaN instead of dm_pow14's values
  *   DM_POW_K     pow14_k(x): 0, NaN and x in [2^-319, 1]
  *   DM_POW_FULL  pow14_lds(x): every double (the slow path outside [2^-319, 1])
- *   DM_POW_Q4G   pow14_q4g(s), DM_POW_KG pow14_kg(x) (ABI 1.10): the same as DM_POW_Q4 / DM_POW_K
- *                bit for bit on EVERY double, from the float32-exponent table rows instead of
- *                the float64 ones (the pruned level kernel, whose LDS holds no gz rows) */
-enum dm_pow_variant { DM_POW_F32 = 0, DM_POW_Q4 = 1, DM_POW_K = 2, DM_POW_FULL = 3, DM_POW_Q4G = 4, DM_POW_KG = 5 };
+ * Any other variant (4 and 5, the pruned level kernel's forms of ABI 1.10, included: that kernel
+ * was removed) fails with DM_ERR_ARG. */
+enum dm_pow_variant { DM_POW_F32 = 0, DM_POW_Q4 = 1, DM_POW_K = 2, DM_POW_FULL = 3 };
 int dm_pow14_variant(int32_t variant, const double *d_in, size_t n, double *d_out, void *stream);
 
 /* Self-test of the exact float32 num = n * sum_k T'_k I'_k - sum(T') * sum(I') from ONE
@@ -817,8 +816,8 @@ int dm_opt_loop_bilateral(double *d_img, const double *d_color, const double *d_
  * error sums. */
 int dm_seq_sum(const double *d_v, int64_t n, double *d_out, void *stream);
 
-/* The compile-time kernel switches this library was built with ("S1=1 C2_NB=4 ..."; see
- * dm_kernels.hip: DM_S1, DM_C*_NB, DM_VL_*), which decide the kernel instance each shape
+/* The compile-time tunables this library was built with ("C2_NB=4 C3_NB=2 ..."; see
+ * dm_kernels.hip: DM_C*_NB, DM_C3_MINW, DM_VL_*), which decide the kernel instance each shape
  * launches -- tools/kernel_hash.py derives the profiled instances' symbols from it. */
 const char *dm_build_config(void);
 
@@ -832,7 +831,9 @@ const char *dm_last_error(void);
  * 4-tile column groups of dm_corr_stats' window operands at S = 128 / 256, 1.7 dm_seq_sum,
  * 1.8 dm_subpix_map, 1.9 dm_subpix_map_tiles and the row-pair strips of dm_corr_stats'
  * workspace for the level kernel's min / max sweep, 1.10 the DM_POW_Q4G / DM_POW_KG forms of
- * dm_pow14_variant).  dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
+ * dm_pow14_variant; those two forms went again with the pruned level kernel they served, the
+ * values 4 and 5 now fail with DM_ERR_ARG like any unknown variant, and the version stays 110).
+ * dm_fb_check, dm_stitch_fb, dm_fill_bytes, dm_fill_holes,
  * dm_stitch_merge, dm_speckle_bytes, dm_filter_speckles, dm_bilateral_bytes,
  * dm_bilateral_filter, dm_median_bytes, dm_median_filter, dm_debug_num_tile_f16,
  * dm_level_num_f16, dm_photo_bytes, dm_photo_score, dm_photo_refine_bytes, dm_photo_refine,

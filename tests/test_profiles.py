@@ -58,6 +58,38 @@ def test_volume_profiles_match_build(key):
         VOLUME[key], d.get('isa_sha16'), cur)
 
 
+@_needs_lib
+def test_level_kernel_instances_are_exactly_the_launchable_ones():
+    """The library holds the k_level1_mfq / k_level12_* instances the dispatch can launch and no
+    other (level_kernel / launch_level in dm_kernels.hip), each for dm_corr_level1 (L2F = 0) and
+    dm_corr_level12 (L2F = 1):
+      ws >= 7            k_level1_mfq<KS, 2, NW, 5, L2F, false>: KS = ceil(ws^2 / 64) = 1 .. 4,
+                         NW = w0 / 32 = 1, 2, 4, 8 (w0 = 32, 64, 128, 256)
+      ws <= 5, w0 = 32   k_level1_mfq<1, 2, 1, 5, L2F, true>: the packed-f32 y (YF); the wider
+                         ws <= 5 shapes all have strips
+      ws <= 5, w0 = 128  k_level1_mfq<1, 4, 2 C3_NB, C3_MINW, L2F, true, C3_NB, F16 = true>
+      ws <= 5, w0 = 64   k_level12_strip<1, C2_NB, L2F>;  w0 = 256: k_level12_strip<4, C5_NB, L2F>
+    A dead instance that comes back (a launch behind a run-time `if` over compile-time constants
+    still instantiates its kernel), or the pruned kernel, fails here."""
+    c = dict(K.DEFAULTS, **K.build_config(LIB))
+    mfq = '_Z12k_level1_mfqILi%dELi%dELi%dELi%dELb%dELb%dELi%dELb%dEE'
+    want = {mfq % (ks, 2, nw, 5, l2f, yf, 1, 0)
+            for ks in (1, 2, 3, 4) for nw in (1, 2, 4, 8) for l2f in (0, 1) for yf in (0, 1)
+            if not yf or (ks, nw) == (1, 1)}
+    want |= {mfq % (1, 4, 2 * c['C3_NB'], c['C3_MINW'], l2f, 1, c['C3_NB'], 1) for l2f in (0, 1)}
+    want |= {'_Z15k_level12_stripILi%dELi%dELb%dEE' % (nwc, c[nb], l2f)
+             for nwc, nb in ((1, 'C2_NB'), (4, 'C5_NB')) for l2f in (0, 1)}
+    assert len(want) == 40
+    data = open(LIB, 'rb').read()
+    have = set()
+    for base in K._elfs(data):
+        syms = K._symbols(data, base)
+        have |= {nm[:nm.index('v3Geo')] for nm in syms
+                 if nm + '.kd' in syms and ('k_level1_mfq' in nm or 'k_level12_' in nm)}
+    assert not any('k_level12_prune' in nm for nm in have)
+    assert have == want, (sorted(have - want), sorted(want - have))
+
+
 def test_hash_masks_pc_relative_table_offsets():
     """The ISA hash ignores the literals of s_getpc_b64 + s_add_u32 / s_addc_u32 (the constant
     tables' PC-relative offsets, which move when another kernel grows) and nothing else."""

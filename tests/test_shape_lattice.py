@@ -1,7 +1,7 @@
 """Every kernel instance the launchers can pick, on at least one small tile, against the oracle.
 
 The library takes any tile with w0 in {32, 64, 128, 256}, h0 % 4 == 0 and ws <= 15 on its MFMA
-paths (mf16_eligible, csrc/dm_mfma.h), and launch_mfq_t / launch_volume_ls / launch_volume_mfq
+paths (mf16_eligible, csrc/dm_mfma.h), and launch_level / launch_volume_ls / launch_volume_mfq
 (csrc/dm_kernels.hip) turn the shape into one of several dozen template instances.  The cases
 below are the smallest tiles that reach each instance, plus the edges the row-pair sweeps have
 (h0 = 4 and 8: every row both top and bottom border), the runtime window side (ws != 5) on the
@@ -60,16 +60,17 @@ def dispatch_key(h0, w0, ws):
     launch rules of csrc/dm_kernels.hip.
 
     level:  (launcher branch, KS, GW, NW, ws == 5)
-        KS, NW, GW          launch_mfq_t :1567, mfq_nw :1323-1329
-        packed y (ws <= 5)  launch_mfq :1635-1636
-        'c5' / 'c2' / 'c3'  the GW = 4 branches :1574, :1588, :1600 (KS == 1, NW = 4 / 1 / 2)
-        'mq_y' / 'mq'       the DM_MQ table :1614-1620 (GW = 2; KS >= 2 only without packed y)
+        KS, NW, GW          launch_level, mfq_nw (strip_shape)
+        packed y (ws <= 5)  launch_level's DM_MQ(1, 1, true)
+        'c5' / 'c2' / 'c3'  level_kernel's LK_STRIP (w0 = 256 / 64) and LK_MFQ_F16 (w0 = 128):
+                            KS == 1, GW == 4, NW = 4 / 1 / 2
+        'mq_y' / 'mq'       LK_MFQ, the DM_MQ table (GW = 2; KS >= 2 only without packed y)
         ws == 5             the compile-time window side of fill_ptab / k_prep_strips /
-                            k_prep_windows16 (dm_mfma.h:600, dm_strip.h:74, :1713, :1845, :1853)
-    volume: ('ls', G, None) launch_volume_ls :1698-1764 (volume_ls_shape :1333-1336), or
-            ('mfq', KS, LS_) launch_volume_mfq :1769-1784 (LS_ = w0 <= 128, GW == 2 only)"""
+                            k_prep_windows16 (dm_mfma.h, dm_strip.h, dm_corr_stats)
+    volume: ('ls', G, None) launch_volume_ls (volume_ls_shape), or
+            ('mfq', KS, LS_) launch_volume_mfq (LS_ = w0 <= 128, GW == 2 only)"""
     if not (h0 % 4 == 0 and w0 in (32, 64, 128, 256) and 1 <= ws <= 15 and ws % 2 == 1):
-        raise ValueError('not an MFMA shape (mf16_eligible, dm_mfma.h:1687): %r' % ((h0, w0, ws),))
+        raise ValueError('not an MFMA shape (mf16_eligible, dm_mfma.h): %r' % ((h0, w0, ws),))
     G, KS = w0 // 16, (ws * ws + 63) // 64
     g4 = ws * ws <= 25 and G % 4 == 0 and G // 4 in (1, 2, 4)
     NW = G // 4 if g4 else min(G // 2, 8)

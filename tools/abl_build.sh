@@ -1,21 +1,10 @@
 #!/bin/bash
-# Ablation builds of the level kernel (timing upper bounds only; their results are WRONG):
-#   nobar   no barrier between the two waves of a workgroup in sweep 2 (dm_mfma.h:628)
+# A/B and ablation builds of the level and volume kernels.  Entries marked "results wrong" are
+# timing bounds only; the others are bit-identical to the in-tree build.  The entries of switches
+# whose question is settled (s0, s2off, s2all, c3mw3, x0, vs0, vs1l2, ssync, prune0/1, f16y,
+# f16y0, papprox, papprox2, and the line-numbered nobar / nosw1) went with their code; commit
+# da6eb20 is the last that builds them.
 #   nopow   pow14_zf replaced by a widening multiply (the eight child pows per row pair)
-#   papprox  (round 6) the child pows replaced by the bin-centre approximation (1/c_i)^y 2^(yE):
-#           the floor of any pruning of the child pows (C3 k_level1_mfq only)
-#   papprox2 the same with 2 of a lane's 8 child pows per row exact: the ideal pruned count (one
-#           exact level-1 value per level-2 window), without the candidate bookkeeping
-#   ssync   (round 6) the strip kernel's one-wave cell blocks (C2) synchronised by workgroup
-#           barriers between the sweeps, as in round 5 (DM_STRIP_WAVESYNC=0; results exact)
-#   prune0, prune1  (round 6) the C3 level kernel without / with the child-pow pruning
-#           (k_level1_mfq / k_level12_prune, DM_PRUNE; results exact)
-#   f16y    sweep 2 of the C3 k_level1_mfq on v_mfma_f32_16x16x32_f16 with y = D * b_q as one packed
-#           multiply, fed today's i8 fragments (DM_ABL_F16Y): the floor of taking num from the f16
-#           MFMA (dm_mfma.h, num_tile_f16) before the operands are built (results wrong)
-#   f16y0   the C3 k_level1_mfq with the i8 tiles and the three-step y in sweep 2, as before num
-#           came from the f16 MFMA (DM_F16Y=0; results exact)
-#   nosw1   sweep 1 (per-patch min / max) skipped
 #   pconst  pow14_zf's three LDS table reads at fixed rows (broadcast: no bank conflicts)
 #   pnoread pow14_zf without its LDS table reads (values from the index bits, no LDS)
 #   prow    c_i and a float32 (1/c_i)^y lo packed into the fp row: one b128 read instead of
@@ -25,20 +14,11 @@
 #           plain (p) stores (DM_VL_H_*; results exact); h2w8 / h2w2: 8 / 2 waves per workgroup (4 in-tree)
 #   f4m, f4mp, f2mp, f4p, f0p   the w0 = 128 float32 volume: runs of 4 / 2 / none, m = compiled
 #           for 4 waves per SIMD, p = plain stores (DM_VL_F_*; results exact)
-#   s0      sweep 1 on the 16 x 16 tiles instead of the row-pair strips (DM_S1=0; results exact)
-#   x0      the level kernel's workgroups in dispatch order, not XCD-grouped (DM_XCD_MAP=0; exact)
-#   s2off   sweep 2 on the 16 x 16 tiles (k_level1_mfq) for every shape (DM_S2=0; results exact)
-#   s2all   the strip kernel (k_level12_strip) for C3 as well (DM_S2=7; results exact)
-#   vs0     the standalone volumes' min/max sweep on the 16 x 16 tiles, not the strips (DM_VS1=0; exact)
-#   c3mw3   the S = 128 strip kernel compiled for 3 waves per SIMD (A, patch sums in registers,
-#           two row pairs per loop trip; DM_C3_MW=3; results exact)
 #   head    the last commit's sources (an A/B of the working tree against it)
 #   hsw4, fw4   the w0 = 128 binary16 standalone / float32 volumes in 4-wave workgroups
 #   smilp, smclause, strack   every kernel scheduled by the AMDGPU machine scheduler's max-ilp /
 #           max-memory-clause strategy, or with the AMDGPU register-pressure trackers (-mllvm
 #           -amdgpu-sched-strategy=..., -amdgpu-use-amdgpu-trackers; results exact: scheduling only)
-#   vs1l2   the standalone volumes' strip min/max sweep with every wave reading the units from
-#           L2 instead of each unit staged in LDS once per workgroup (DM_VS1_LDS=0; exact)
 #   hs4t2, hs8t2   the binary16 standalone volume in 4- / 8-wave workgroups with 2 x 512-B runs per
 #           store (DM_VL_HS_NW, DM_VL_HS_TR; results exact)
 #   c5h2w4, c5f4m   the w0 = 256 volumes: binary16 min/max known with 2 x 512-B runs in
@@ -64,7 +44,6 @@ FLAGS="-O3 -std=c++17 -ffp-contract=off -fPIC -shared -Wno-pass-failed -mllvm -a
 for v in "$@"; do
   EXTRA=""; r=/tmp/abl_$v; rm -rf $r; d=$r/pkg; mkdir -p $d; cp -r $REPO/deepmatching_stereo_matching_amd/csrc $d/; cp -r $REPO/include $r/
   case $v in
-    nobar) sed -i '628s/__syncthreads();/__builtin_amdgcn_wave_barrier();/' $d/csrc/dm_mfma.h ;;
     nopow) python3 - $d/csrc/dm_kernels.hip <<'PY'
 import sys
 p = sys.argv[1]; s = open(p).read()
@@ -74,13 +53,6 @@ s = s[:a] + '__device__ __forceinline__ double pow14_zf(float x, const T &t, uns
 open(p, 'w').write(s)
 PY
     ;;
-    papprox) EXTRA="-DDM_ABL_PAPPROX=1" ;;
-    f16y) EXTRA="-DDM_F16Y=0 -DDM_ABL_F16Y=1" ;;
-    f16y0) EXTRA="-DDM_F16Y=0" ;;
-    ssync) EXTRA="-DDM_STRIP_WAVESYNC=0" ;;
-    prune0) EXTRA="-DDM_PRUNE=0" ;;
-    prune1) EXTRA="-DDM_PRUNE=1" ;;
-    papprox2) EXTRA="-DDM_ABL_PAPPROX=2" ;;
     clk) EXTRA="-DDM_CLOCK_STAMP=1" ;;
     bwrow0) sed -i 's/^            const unsigned ti = (unsigned)q0 \* G + tw;$/            const unsigned ti = (unsigned)(q0 \& (g.h0 >> 16)) * G + tw;/' $d/csrc/dm_mfma.h
             grep -q "(unsigned)(q0 & (g.h0 >> 16)) \* G + tw;" $d/csrc/dm_mfma.h || { echo "bwrow0 patch failed"; exit 1; } ;;
@@ -88,7 +60,6 @@ PY
             grep -q "(unsigned)((rp & (g.h0 >> 16)) \* NT32 + j) \* 1024u" $d/csrc/dm_mfma.h || { echo "strow0 patch failed"; exit 1; } ;;
     nofill) sed -i 's/^    pow_lds_fill(plds, tid, 64 \* NW, false);$/    (void)plds;/' $d/csrc/dm_strip.h
             grep -q "^    (void)plds;" $d/csrc/dm_strip.h || { echo "nofill patch failed"; exit 1; } ;;
-    nosw1) sed -i '457s/q0 < h0; q0 += 2) {/q0 < 0; q0 += 2) {/' $d/csrc/dm_mfma.h ;;
     pconst) sed -i 's/    const unsigned ofp = (u >> 10) \& 0x1FF0u, og = (u >> 19) \& 0xFF0u;/    const unsigned ofp = (u \& 0u), og = (u \& 0u) + 16u;/' $d/csrc/dm_kernels.hip
             grep -q "ofp = (u & 0u)" $d/csrc/dm_kernels.hip || { echo "pconst patch failed"; exit 1; } ;;
     pnoread) python3 - $d/csrc/dm_kernels.hip <<'PY'
@@ -124,7 +95,6 @@ PY
     smilp) EXTRA="-mllvm -amdgpu-sched-strategy=max-ilp" ;;
     smclause) EXTRA="-mllvm -amdgpu-sched-strategy=max-memory-clause" ;;
     strack) EXTRA="-mllvm -amdgpu-use-amdgpu-trackers" ;;
-    vs1l2) EXTRA="-DDM_VS1_LDS=0" ;;
     hs4t2) EXTRA="-DDM_VL_HS_NW=4 -DDM_VL_HS_TR=2" ;;
     hs8t2) EXTRA="-DDM_VL_HS_NW=8 -DDM_VL_HS_TR=2" ;;
     h2n) EXTRA="-DDM_VL_H_TR=2" ;;
@@ -147,12 +117,6 @@ PY
     c3nb4) EXTRA="-DDM_C3_NB=4" ;;
     c5nb2) EXTRA="-DDM_C5_NB=2" ;;
     c2nb8) EXTRA="-DDM_C2_NB=8" ;;
-    s0) EXTRA="-DDM_S1=0" ;;
-    x0) EXTRA="-DDM_XCD_MAP=0" ;;
-    s2off) EXTRA="-DDM_S2=0" ;;
-    s2all) EXTRA="-DDM_S2=7" ;;
-    c3mw3) EXTRA="-DDM_S2=7 -DDM_C3_MW=3" ;;
-    vs0) EXTRA="-DDM_VS1=0" ;;
     head) rm -rf $d/csrc $r/include; mkdir -p $d/csrc $r/include
           (cd $REPO && for f in $(git ls-files deepmatching_stereo_matching_amd/csrc include); do
              case $f in include/*) git show HEAD:$f > $r/$f ;; *) git show HEAD:$f > $d/csrc/$(basename $f) ;; esac; done) ;;

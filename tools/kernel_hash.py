@@ -19,18 +19,19 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EM_AMDGPU = 224
 
 # The kernel instance each profiled shape launches depends on the library's compile-time
-# switches (dm_kernels.hip: DM_S1, DM_S2, DM_C*_NB, DM_VL_*), which the library reports through
+# tunables (dm_kernels.hip: DM_C*_NB, DM_C3_MINW, DM_VL_*), which the library reports through
 # dm_build_config(); the symbols below are derived from it, so an A/B build made with -D
-# overrides (tools/abl_build.sh) is looked up under its own instances.  A library without
-# dm_build_config (before round 5) uses the round-4 instances (LEGACY).
+# overrides (tools/abl_build.sh) is looked up under its own instances.  A library that still
+# reports the A/B switches removed after da6eb20 (S1, S2, F16Y, ...: a parent-commit build) is
+# looked up under that commit's longer template lists, at the values it shipped with.  A library
+# without dm_build_config (before round 5) uses the round-4 instances (LEGACY).
 LEVEL = (64, 128, 256)       # profiled level-kernel tiles: C2, C3, C5
 VOLUME = ((128, 4, False), (128, 4, True), (128, 2, False), (128, 2, True),
           (256, 4, False), (256, 4, True), (256, 2, False), (256, 2, True))
 # DEFAULTS mirror the C defaults of dm_kernels.hip (every key dm_build_config reports); they
 # only fill keys a library's config string lacks -- a library that cannot be loaded at all is
 # an error (symbol() raises), never a guess.
-DEFAULTS = {'S1': 1, 'F16Y': 1, 'S2': 5, 'PRUNE': 0, 'STRIP_WAVESYNC': 0, 'VS1': 1, 'VS1_LDS': 1, 'XCD_MAP': 1, 'C2_NB': 4, 'C3_NB': 2, 'C3_MW': 4,
-            'C3_MINW': 4, 'C5_NB': 1, 'VL_H_TR': 2, 'VL_H_NT': 1, 'VL_H_NW': 4,
+DEFAULTS = {'C2_NB': 4, 'C3_NB': 2, 'C3_MINW': 4, 'C5_NB': 1, 'VL_H_TR': 2, 'VL_H_NT': 1, 'VL_H_NW': 4,
             'VL_H2_TR': 0, 'VL_H2_NW': 8, 'VL_F2_TR': 0, 'VL_F2_MW': 1, 'VL_HS_NW': 8, 'VL_HS_TR': 0,
             'VL_F_NW': 8, 'VL_F_TR': 4, 'VL_F_MW': 4, 'VL_F_NT': 1}
 LEGACY = {('level', 64): 'k_level1_mfqILi1ELi4ELi4ELi4ELb1ELb1ELi4ELb1EE',
@@ -45,7 +46,7 @@ def _lib_path(lib=None):
 
 
 def build_config(lib=None):
-    """The library's compile-time switches as a dict (dm_build_config()); None if the library
+    """The library's compile-time tunables as a dict (dm_build_config()); None if the library
     cannot be loaded, {} if it predates dm_build_config."""
     path = _lib_path(lib)
     if path not in _CONFIG:
@@ -77,18 +78,14 @@ def symbol(kind, tile, esz=None, mm=False, lib=None):
     if kind == 'level':
         if tile not in LEVEL:
             return None
+        # level_kernel / launch_level (dm_kernels.hip), fused with level 2 (L2F = true)
         nb = c['C2_NB'] if tile == 64 else c['C3_NB'] if tile == 128 else c['C5_NB']
         nwc = 1 if tile == 64 else 2 if tile == 128 else 4
-        if (c['S2'] >> {64: 0, 128: 1, 256: 2}[tile]) & 1:   # both sweeps on the strips (dm_strip.h)
-            return 'k_level12_stripILi%dELi%dELb1ELb1ELi%dEE' % (nwc, nb, c['C3_MW'] if tile == 128 else 4)
-        if tile == 128 and c['PRUNE']:   # round 6: the pruned C3 kernel (dm_prune.h), when built in
-            return 'k_level12_pruneILi2ELi%dELi%dEE' % (nb, c['C3_MINW'])
-        minw = c['C3_MINW'] if tile == 128 else 4
-        if 'F16Y' not in cfg:   # before the F16 template flag of k_level1_mfq
-            return 'k_level1_mfqILi1ELi4ELi%dELi%dELb1ELb1ELi%dELb1ELb%dEE' % (nb * nwc, minw, nb, c['S1'])
-        # f16y_shape (dm_kernels.hip): num from the f16 MFMA in sweep 2 of the w0 = 128 instance
-        f16 = int(tile == 128 and bool(c['F16Y']) and bool(c['S1']))
-        return 'k_level1_mfqILi1ELi4ELi%dELi%dELb1ELb1ELi%dELb1ELb%dELb%dEE' % (nb * nwc, minw, nb, c['S1'], f16)
+        old = 'S2' in cfg   # up to da6eb20: k_level12_strip<.., CL, MINW>, k_level1_mfq<.., CL, S1, F16>
+        if tile != 128:     # both sweeps on the strips (dm_strip.h): <NWc, NB, L2F>
+            return 'k_level12_stripILi%dELi%dELb1E%s' % (nwc, nb, 'Lb1ELi4EE' if old else 'E')
+        # the F16 instance: <KS = 1, GW = 4, NW, MINW, L2F, YF, NB, F16>
+        return 'k_level1_mfqILi1ELi4ELi%dELi%dELb1ELb1ELi%dE%sLb1EE' % (nb * nwc, c['C3_MINW'], nb, 'Lb1ELb1E' if old else '')
     if (tile, esz, bool(mm)) not in VOLUME:
         return None
     if tile == 128 and esz == 4:

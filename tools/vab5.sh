@@ -1,6 +1,6 @@
 #!/bin/bash
-# Same-box A/B of the volume kernels for library builds (round 5: the min/max sweep on the
-# row-pair strips, DM_VS1), two interleaved passes, each run printing the volume checksum:
+# Same-box A/B of the volume kernels for library builds (written in round 5 for the min/max
+# sweep on the row-pair strips), two interleaved passes, each run printing the volume checksum:
 # C3 (64 tiles of S = 128) float32 / binary16 standalone and min/max known, C5-size (4 / 8
 # tiles of S = 256) float32 / binary16 standalone.
 #   usage (GPU box): bash tools/vab5.sh lib1.so lib2.so ...

@@ -18,6 +18,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DM_LIB_PATH') or os.path.join(HERE, 'libdmstereo.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'dmstereo.h')
 HEADER_SGM = os.path.join(os.path.dirname(HERE), 'include', 'dmstereo_sgm.h')   # dm_sgm_refine: a header of its own
+HEADER_LSM = os.path.join(os.path.dirname(HERE), 'include', 'dmstereo_lsm.h')   # dm_lsm_affine likewise
 
 DM_OK, DM_ERR_ARG, DM_ERR_SHAPE, DM_ERR_UNSUPPORTED, DM_ERR_HIP = 0, -1, -2, -3, -4
 DM_VOLUME_F16, DM_VOLUME_MINMAX_KNOWN = 1, 2   # dm_corr_volume_ex flags
@@ -116,6 +117,9 @@ SIGNATURES = {
     'dm_sgm_bytes': ([_I, _I, _I, _I], ctypes.c_size_t),
     'dm_sgm_refine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I,
                        _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
+    'dm_lsm_affine_bytes': ([_I, _I, _I, _I, _I, _I], ctypes.c_size_t),
+    'dm_lsm_affine': ([_P, ctypes.c_int64, _P, ctypes.c_int64, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I,
+                       ctypes.c_double, ctypes.c_double, _I, _P, _P, _P, _P, _P, _P, _P, _P], ctypes.c_int),
     'dm_downsample2': ([_P, ctypes.c_int64, _I, _I, _P, ctypes.c_int64, _P], ctypes.c_int),
     'dm_tile_prior': ([_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P], ctypes.c_int),
     'dm_pack_plan': ([_I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),

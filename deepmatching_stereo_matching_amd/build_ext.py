@@ -21,9 +21,10 @@ SOURCES = [os.path.join(CSRC, 'dm_kernels.hip'), os.path.join(CSRC, 'dm_postproc
            os.path.join(CSRC, 'dm_bilateral.hip'), os.path.join(CSRC, 'dm_median.hip'),
            os.path.join(CSRC, 'dm_photo.hip'), os.path.join(CSRC, 'dm_photo_refine.hip'),
            os.path.join(CSRC, 'dm_lsm.hip'), os.path.join(CSRC, 'dm_prior.hip'),
-           os.path.join(CSRC, 'dm_sgm.hip')]
+           os.path.join(CSRC, 'dm_sgm.hip'), os.path.join(CSRC, 'dm_lsm_affine.hip')]
 DEPS = SOURCES + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + \
-    [os.path.join(REPO, 'include', 'dmstereo.h'), os.path.join(REPO, 'include', 'dmstereo_sgm.h')]
+    [os.path.join(REPO, 'include', 'dmstereo.h'), os.path.join(REPO, 'include', 'dmstereo_sgm.h'),
+     os.path.join(REPO, 'include', 'dmstereo_lsm.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = os.environ.get('PYTORCH_ROCM_ARCH', 'gfx950')
 FLAGS = ['-O3', '-std=c++17', '-ffp-contract=off', '-fPIC', '-shared', '-Wno-pass-failed',

@@ -19,14 +19,17 @@ optional, works on d_map [len(modes)][H][W] in place and is switched on by its k
                 refine_where='filled'; adds `refine_score` and the int8 `refine_shift`.
   lsm           engine.lsm_refine on the two elevation planes: the least-squares sub-pixel
                 step, of the filled cells only with lsm_where='filled'; adds `lsm_score` and
-                the int8 `lsm_status`.
+                the int8 `lsm_status`.  With lsm_model='affine' or ('affine', max_shear) the
+                stage is engine.lsm_affine, which also solves for the stretch and shear of the
+                window, and adds the float64 `lsm_affine` [4][H][W] after them; its hook gets
+                max_shear after max_move and returns the affine planes as a fifth value.
   smooth        engine.bilateral_filter, guided by img1 under the map's cells (smooth_guide
                 'image') or by the map itself ('self'); holes stay holes.
   photo score   with photo=: adds `score`, the photo-consistency of the final d_map.
 
 The result is a tuple in the order of Chain.layout -- not the order the stages run in:
 (d_map, out_map[, err][, spread, count][, speckles][, holes][, sgm_score, sgm_shift]
-[, refine_score, refine_shift][, lsm_score, lsm_status][[, rejected], score]).  A stage may be
+[, refine_score, refine_shift][, lsm_score, lsm_status[, lsm_affine]][[, rejected], score]).  A stage may be
 replaced by a host function (the hooks of solve_image_sharded); the calls are the ones written in
 the stage functions below.
 """
@@ -99,13 +102,18 @@ def _plane(st, c, v, r):
     d = v['d_map']
     holes = v['holes'] if getattr(c, st.key + '_where') == 'filled' else None
     hook = getattr(r, st.hook)
+    stage, outs = st.stage, [st.key + '_score', st.aux]
+    if st is LSM and c.lsm_model[0] == 'affine':      # max_shear follows max_move; the affine planes are one more result
+        p, stage, outs = p + (c.lsm_model[1],), 'lsm_affine_stage', outs + ['lsm_affine']
     if hook is not None:
         row, col = engine.refine_planes(c.modes)
         mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
-        d[row], d[col], v[st.key + '_score'], v[st.aux] = hook(r.img1, r.img2, d[row], d[col], p[0], p[1], r.e, *p[2:],
-                                                               mask)
+        d[row], d[col], *rest = hook(r.img1, r.img2, d[row], d[col], p[0], p[1], r.e, *p[2:], mask)
     else:
-        v['d_map'], v[st.key + '_score'], v[st.aux] = getattr(engine, st.stage)(r.img1, r.img2, d, c.modes, p, r.e, holes)
+        v['d_map'], *rest = getattr(engine, stage)(r.img1, r.img2, d, c.modes, p, r.e, holes)
+    if len(rest) != len(outs):
+        raise ValueError('the %s stage returns %d tensors after the planes, not %d' % (st.key, len(outs), len(rest)))
+    v.update(zip(outs, rest))
 
 
 _sgm, _refine, _lsm = (partial(_plane, st) for st in PLANE_STAGES)
@@ -144,7 +152,7 @@ class Chain:
 
     def __init__(self, modes, fill=None, speckle=None, smooth=None, smooth_guide='image', median=None,
                  median_weight=None, photo=None, refine=None, refine_where='filled', lsm=None, lsm_where='all',
-                 sgm=None, sgm_where='all'):
+                 sgm=None, sgm_where='all', lsm_model='shift'):
         self.modes = modes
         self.fill = engine.fill_iterations(fill) if fill is not None else None
         self.speckle = engine.speckle_params(speckle) if speckle is not None else None
@@ -166,6 +174,10 @@ class Chain:
             if p is not None:
                 engine.refine_planes(modes)
                 engine.refine_where(where, self.fill, st.key + '_where')
+        self.lsm_model = engine.lsm_model_params(lsm_model)      # validated even when lsm is None
+        if self.lsm is not None and self.lsm_model[0] == 'affine' and self.lsm[0] < 2:
+            raise ValueError('lsm radius must be in [2, 7] with lsm_model=\'affine\': nine taps cannot carry eight '
+                             'unknowns (got %r)' % (self.lsm[0],))
 
     def layout(self, H, W, consistency, merge):
         """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
@@ -184,6 +196,8 @@ class Chain:
         for st in PLANE_STAGES:
             if getattr(self, st.key) is not None:
                 lay += [(st.key + '_score', (H, W), f64), (st.aux, st.lead + (H, W), torch.int8)]
+                if st is LSM and self.lsm_model[0] == 'affine':
+                    lay.append(('lsm_affine', (4, H, W), f64))
         if self.photo is not None:
             if self.photo[1] is not None:
                 lay.append(('rejected', (H, W), u8))

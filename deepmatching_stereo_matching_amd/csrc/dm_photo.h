@@ -1,5 +1,7 @@
 // dm_photo.h -- what the four stages that read the image pair share: dm_photo.hip (dm_photo_score),
 // dm_photo_refine.hip (dm_photo_refine), dm_lsm.hip (dm_lsm_refine) and dm_sgm.hip (dm_sgm_refine).
+// dm_lsm_affine.hip (dm_lsm_affine), the affine model of the lsm stage, uses the host side, pho_cell,
+// pho_bilin, pho_numvb and pho_zncc.
 //
 // Host side, used by all four entries:
 //   pho_pair_args   the argument checks they have in common (image shape, strides, map shape, offset,

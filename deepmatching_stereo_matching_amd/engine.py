@@ -1089,13 +1089,15 @@ def _plane_out(out, d_row):
 
 
 def _rematch(entry, bytes_call, img1, img2, d_row, d_col, offset, mask, out, scalars, return_score, aux_shape, stream,
-             unsupported_msg):
+             unsupported_msg, extra_shape=False):
     """The body of the plane re-matching entries (photo_refine, lsm_refine, sgm_refine), whose C entries
     share one argument layout: the pair, the planes, the map shape and the offset, then the stage's
     ``scalars``, then mask, the two output planes, the score, the int8 plane of ``aux_shape`` (None: not
     asked for), the workspace and the stream.  ``bytes_call(lib, Hi, Wi, H, W)``: the workspace size;
-    ``unsupported_msg``: NotImplementedError's text, a template over H, W, Hi, Wi.
-    -> (d_row', d_col', score or None, aux or None)."""
+    ``unsupported_msg``: NotImplementedError's text, a template over H, W, Hi, Wi.  ``extra_shape``: for an entry
+    that takes one more float64 output between the int8 plane and the workspace (dm_lsm_affine), its shape or
+    None (not asked for); the tensor is then a fifth result.
+    -> (d_row', d_col', score or None, aux or None[, extra or None])."""
     dev = _planes_device(d_row, d_col)
     oy, ox = _offset(offset)
     _plane_mask(mask, d_row)
@@ -1107,6 +1109,8 @@ def _rematch(entry, bytes_call, img1, img2, d_row, d_col, offset, mask, out, sca
                                                     torch.empty((H, W), dtype=torch.float64, device=dev))
         score = torch.empty((H, W), dtype=torch.float64, device=dev) if return_score else None
         aux = torch.empty(aux_shape, dtype=torch.int8, device=dev) if aux_shape is not None else None
+        extra = torch.empty(extra_shape, dtype=torch.float64, device=dev) if extra_shape else None
+        more = () if extra_shape is False else (L.ptr(extra),)
         if H and W:
             if not a.numel():
                 raise ValueError('empty image')
@@ -1117,18 +1121,18 @@ def _rematch(entry, bytes_call, img1, img2, d_row, d_col, offset, mask, out, sca
             rows, cols = _held_planes(d_row, d_col)
             L.check(getattr(lib, entry)(L.ptr(a), a.stride(0), L.ptr(b), b.stride(0), Hi, Wi, L.ptr(rows), L.ptr(cols),
                                         H, W, int(oy), int(ox), *scalars, L.ptr(m), L.ptr(o_row), L.ptr(o_col),
-                                        L.ptr(score), L.ptr(aux), L.ptr(work), L.stream_handle()), entry)
-    return o_row, o_col, score, aux
+                                        L.ptr(score), L.ptr(aux), *more, L.ptr(work), L.stream_handle()), entry)
+    return (o_row, o_col, score, aux) if extra_shape is False else (o_row, o_col, score, aux, extra)
 
 
 def _plane_stage(fn, img1, img2, d_map, modes, holes, *args, **kw):
     """A plane re-matching stage of the chain on the stitched d_map [len(modes)][H][W], in place: ``fn`` on
     the two elevation planes, of the cells that ``holes`` marks in either (None: every cell).
-    -> (d_map, score, the stage's int8 plane)."""
+    -> (d_map, score, the stage's int8 plane[, what else ``fn`` returns])."""
     ir, ic = refine_planes(modes)
     mask = None if holes is None else (holes[ir] | holes[ic])
-    _, _, score, aux = fn(img1, img2, d_map[ir], d_map[ic], *args, mask=mask, out=(d_map[ir], d_map[ic]), **kw)
-    return d_map, score, aux
+    res = fn(img1, img2, d_map[ir], d_map[ic], *args, mask=mask, out=(d_map[ir], d_map[ic]), **kw)
+    return (d_map,) + tuple(res[2:])
 
 
 def photo_planes(modes):
@@ -1332,6 +1336,62 @@ def lsm_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
     (lsm_where='filled') -- or None: every cell.  -> (d_map, score, int8 status [H][W])."""
     return _plane_stage(lsm_refine, img1, img2, d_map, modes, holes, lsm[0], lsm[1], offset=offset, max_move=lsm[2],
                         return_score=True, return_status=True)
+
+
+def lsm_model_params(model):
+    """The ``lsm_model=`` keyword of ImageCutSolver / shard.solve_image_sharded as (name, max_shear):
+    ``'shift'`` -> ('shift', None), the two-parameter solve of lsm_refine; ``'affine'`` or
+    ``('affine', max_shear)`` -> ('affine', max_shear), the six-parameter solve of lsm_affine with
+    max_shear a real in (0, 1) (0.5 in the first form).  The parsed tuples are taken as well."""
+    if isinstance(model, (tuple, list)) and len(model) == 2 and isinstance(model[0], str):
+        name, shear = model
+    elif isinstance(model, str):
+        name, shear = model, (0.5 if model == 'affine' else None)
+    else:
+        name = shear = None
+    if name == 'shift' and shear is None:
+        return 'shift', None
+    if name != 'affine':
+        raise ValueError("lsm_model must be 'shift', 'affine' or ('affine', max_shear) (got %r)" % (model,))
+    shear = _real_in(shear, 0.0, 1.0, 'lsm_model max_shear must be a real in (0, 1) (got %r)', open_lo=True)
+    if not shear < 1.0:
+        raise ValueError('lsm_model max_shear must be a real in (0, 1) (got %r)' % (model[1],))
+    return 'affine', shear
+
+
+def lsm_affine(img1, img2, d_row, d_col, radius, iters, offset=0, max_move=1.0, max_shear=0.5, mask=None, out=None,
+               return_score=False, return_status=False, return_affine=False, stream=None):
+    """Affine least-squares matching of a disparity map (dm_lsm_affine, include/dmstereo_lsm.h).
+    Arguments as lsm_refine, but ``radius`` in [2, 7].  Every cell solves ``iters`` times for the
+    affine warp -- the shift of lsm_refine plus stretch and shear on both axes -- under which img2
+    best explains its img1 window: tap (u, v) of the window is sampled at X = px + (1 + a) u + b v,
+    Y = py + c u + (1 + d) v.  On a slope of the terrain, where the disparity changes across the
+    window, the shift-only solve is biased; this one is not.  The new position is kept if the
+    correlation under the final warp is strictly higher than photo_score's at the start and no step
+    left the square of half-side ``max_move`` around the start, the image, or |a|, |b|, |c|, |d| <=
+    ``max_shear`` (a real in (0, 1)).  Every other cell keeps its bits.
+    -> (d_row', d_col'); then, when asked for, the float64 score, the int8 status [H][W] (as
+    lsm_refine's; -1 also for a window whose texture cannot carry six parameters) and the float64
+    affine values [4][H][W] (a, b, c, d; NaN unless accepted) are appended: -a and -d are the
+    disparity gradients along the columns and along the rows."""
+    _planes_device(d_row, d_col)
+    radius, iters, max_move = lsm_params((radius, iters, max_move))
+    if radius < 2:
+        raise ValueError('lsm radius must be an int in [2, 7] for the affine model (got %r)' % (radius,))
+    max_shear = lsm_model_params(('affine', max_shear))[1]
+    res = _rematch('dm_lsm_affine', lambda lib, Hi, Wi, H, W: lib.dm_lsm_affine_bytes(Hi, Wi, H, W, radius, iters),
+                   img1, img2, d_row, d_col, offset, mask, out, (radius, iters, max_move, max_shear, 0), return_score,
+                   tuple(d_row.shape) if return_status else None, stream,
+                   'lsm_affine does not take %(H)d x %(W)d cells on a %(Hi)d x %(Wi)d image',
+                   extra_shape=(4,) + tuple(d_row.shape) if return_affine else None)
+    return tuple(t for t in res if t is not None)
+
+
+def lsm_affine_stage(img1, img2, d_map, modes, lsm, offset, holes=None):
+    """lsm_stage under lsm_model='affine': ``lsm`` is lsm_params' tuple with max_shear appended.
+    -> (d_map, score, int8 status [H][W], float64 affine [4][H][W])."""
+    return _plane_stage(lsm_affine, img1, img2, d_map, modes, holes, lsm[0], lsm[1], offset=offset, max_move=lsm[2],
+                        max_shear=lsm[3], return_score=True, return_status=True, return_affine=True)
 
 
 def sgm_params(sgm):

@@ -47,7 +47,8 @@ class ImageCutSolver():
         lsm=None,
         lsm_where='all',
         sgm=None,
-        sgm_where='all'
+        sgm_where='all',
+        lsm_model='shift'
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -112,6 +113,10 @@ class ImageCutSolver():
         #       and keeps it if the photo-consistency score rises.  lsm_where: 'all' or 'filled' (needs
         #       fill=).  The modes as for refine.  lsm_score_map is the score of the position kept (NaN: not
         #       scored), lsm_status_map the int8 status [H][W] (iters: accepted, 0: skipped, < 0: kept)
+        #   lsm_model: 'shift' (the default), 'affine' or ('affine', max_shear): with 'affine' the lsm stage also
+        #       solves for the stretch and shear of the window (engine.lsm_affine; radius >= 2), which removes the
+        #       bias of the shift on sloped terrain.  lsm_affine_map is then the float64 [4][H][W] of (a, b, c, d),
+        #       NaN unless accepted: -a and -d are the disparity gradients along the columns and the rows
         #   sgm: (radius, search, p1, p2) or (radius, search, p1, p2, paths) of the semi-global re-matching after
         #       the fill and before the refine stage: the cells snap to integer positions and are matched again
         #       together, the (2 search + 1)^2 candidates' costs and a smoothness term (p1 for a step of one pixel
@@ -122,14 +127,14 @@ class ImageCutSolver():
         self.chain = chain.Chain(degree_map_mode, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide,
                                  median=median, median_weight=median_weight, photo=photo, refine=refine,
                                  refine_where=refine_where, lsm=lsm, lsm_where=lsm_where, sgm=sgm,
-                                 sgm_where=sgm_where)
+                                 sgm_where=sgm_where, lsm_model=lsm_model)
         self._sgm_given = sgm      # the shard path parses the keyword itself: it gets what this solver was given
         for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
-                     'refine_where', 'lsm', 'lsm_where', 'sgm', 'sgm_where'):
+                     'refine_where', 'lsm', 'lsm_where', 'sgm', 'sgm_where', 'lsm_model'):
             setattr(self, name, getattr(self.chain, name))
         self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
         self.refine_score_map = self.refine_shift_map = None
-        self.lsm_score_map = self.lsm_status_map = None
+        self.lsm_score_map = self.lsm_status_map = self.lsm_affine_map = None
         self.sgm_score_map = self.sgm_shift_map = None
         # Disparity priors (engine.solve_tiles_prior): tile t's crop of img2 is cut at its origin minus
         # the expected disparity, so that a match outside the tile's own window of img2 can be found.
@@ -239,7 +244,7 @@ class ImageCutSolver():
                                              smooth_guide=self.smooth_guide, median=self.median,
                                              median_weight=self.median_weight, photo=self.photo,
                                              refine=self.refine, refine_where=self.refine_where,
-                                             lsm=self.lsm, lsm_where=self.lsm_where,
+                                             lsm=self.lsm, lsm_where=self.lsm_where, lsm_model=self.lsm_model,
                                              sgm=self._sgm_given, sgm_where=self.sgm_where,
                                              prior=self.prior, coarse=self.coarse)
         if self.prior is not None or self.coarse is not None:
@@ -289,6 +294,7 @@ class ImageCutSolver():
              'sgm_score_map': ('sgm_score', False), 'sgm_shift_map': ('sgm_shift', False),
              'refine_score_map': ('refine_score', False), 'refine_shift_map': ('refine_shift', False),
              'lsm_score_map': ('lsm_score', False), 'lsm_status_map': ('lsm_status', False),
+             'lsm_affine_map': ('lsm_affine', False),
              'photo_reject_map': ('rejected', True),   # the cells scoring below min_score (before any fill)
              'photo_map': ('score', False)}
 

@@ -387,7 +387,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
                         smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
                         medianer=None, photo=None, photoer=None, refine=None, refine_where='filled',
                         refiner=None, prior=None, coarse=None, lsm=None, lsm_where='all', lsmer=None,
-                        sgm=None, sgm_where='all', sgmer=None):
+                        sgm=None, sgm_where='all', sgmer=None, lsm_model='shift'):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -449,7 +449,10 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     (engine.lsm_refine with the offset e, or ``lsmer(img1, img2, d_row, d_col, radius, iters, e,
     max_move, mask or None) -> (d_row, d_col, score, int8 status [H][W])``).  ``lsm_where``: 'all' or
     'filled' (needs ``fill``).  The float64 score [H][W] and the status come immediately after the
-    refine tensors.  None: nothing changes.
+    refine tensors.  None: nothing changes.  ``lsm_model``: 'shift' (the default: today's stage, bit for
+    bit), 'affine' or ('affine', max_shear): engine.lsm_affine, radius >= 2, or ``lsmer(img1, img2, d_row,
+    d_col, radius, iters, e, max_move, max_shear, mask or None) -> (d_row, d_col, score, status, float64
+    affine [4][H][W])``; the affine planes follow the status.  Validated even when ``lsm`` is None.
     ``sgm``: (radius, search, p1, p2) or (radius, search, p1, p2, paths), the modes as for ``refine``;
     rank 0 then matches the cells again together after the fill and before the refine stage
     (engine.sgm_refine with the offset e, or ``sgmer(img1, img2, d_row, d_col, radius, search, e, p1,
@@ -468,7 +471,7 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
         raise ValueError("result must be 'all' or 'root'")
     post = chain.Chain(modes, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide, median=median,
                        median_weight=median_weight, photo=photo, refine=refine, refine_where=refine_where,
-                       lsm=lsm, lsm_where=lsm_where, sgm=sgm, sgm_where=sgm_where)
+                       lsm=lsm, lsm_where=lsm_where, sgm=sgm, sgm_where=sgm_where, lsm_model=lsm_model)
     pair = img1, img2      # what the stages read (consistency stacks the pair below)
     if merge is not None:
         engine.merge_rule(merge)

@@ -176,3 +176,40 @@ def content_pair(kind, h, w, seed):
     else:
         img2 = f[:, 3:].copy()
     return img1, img2
+
+
+def ramp_pair(h, w, seed, g, axis=1, d0=2.0, up=8, noise=0.0):
+    """Return (img1, img2, d), uint8 (h, w) twice and float64 (h, w): a pair whose disparity is a
+    linear ramp of slope ``g`` along the columns (a slope of the terrain), and the true disparity.
+    The texture is generated at ``up`` times the resolution with sigma = up; img1 is every up-th
+    pixel of it; img2(y, x) is the texture at the column x + d0 + g (x - w / 2), interpolated
+    linearly between the two nearest pixels of the fine grid and rounded.  The texture is padded on
+    both sides so that no index leaves it.  img1's column x1 is seen in img2 at x2 = (x1 - d0 +
+    g w / 2) / (1 + g), so the true d_map is d = x1 - x2 in 'elevation' and 0 in 'elevation2', and
+    the matched window is stretched by dx2/dx1 = 1 / (1 + g).  ``axis=0`` builds the pair of (w, h)
+    and transposes it: the ramp runs along the rows, d belongs to 'elevation2' and 'elevation' is 0.
+    With ``noise`` > 0 Gaussian noise of that sigma is added to both images, rounded and clipped.
+    The random draws, in this order: texture(up h, up (w + pad), seed, sigma=up) with its own
+    generator; then, with noise, from default_rng([seed, 3]) one normal draw of shape (h, w) for
+    img1, then one for img2 (before the transposition of axis=0)."""
+    if axis == 0:
+        a, b, d = ramp_pair(w, h, seed, g, 1, d0, up, noise)
+        return a.T.copy(), b.T.copy(), d.T.copy()
+    if axis != 1:
+        raise ValueError('axis must be 0 or 1')
+    if not g > -1.0:
+        raise ValueError('ramp_pair needs a slope g > -1')
+    xx = np.arange(w, dtype=np.float64)
+    s = d0 + g * (xx - w / 2.0)
+    left, right = int(np.ceil(max(0.0, -s.min()))) + 1, int(np.ceil(max(0.0, s.max()))) + 2
+    tex = texture(up * h, up * (w + left + right), seed, sigma=float(up))[0:up * h:up].astype(np.float64)
+    img1 = tex[:, up * left:up * (left + w):up]
+    pos = up * (left + xx + s)
+    i0 = np.floor(pos).astype(np.int64)
+    f = pos - i0
+    img2 = np.rint((1.0 - f) * tex[:, i0] + f * tex[:, i0 + 1])
+    if noise > 0:
+        rng = np.random.default_rng([seed, 3])
+        img1, img2 = _noisy(img1, rng, noise), _noisy(img2, rng, noise)
+    d = xx - (xx - d0 + g * w / 2.0) / (1.0 + g)
+    return img1.astype(np.uint8), img2.astype(np.uint8), np.tile(d, (h, 1))

@@ -1,37 +1,16 @@
 """The post-processing chain of a stitched d_map, for ImageCutSolver and shard.solve_image_sharded.
 
-The chain is stitch -> median -> photo reject -> speckle -> fill -> sgm -> refine -> lsm -> smooth
--> photo score (STAGES below is that order in code).  The caller stitches; every stage after that is
-optional, works on d_map [len(modes)][H][W] in place and is switched on by its keyword:
-
-  median        engine.median_filter, all modes in one call, weighted by out_map when
-                median_weight is 'correlation'; holes stay holes.
-  photo reject  with photo=(radius, min_score): the cells whose photo-consistency score
-                (engine.photo_score, map cell (y, x) at image pixel (y + e, x + e)) is below
-                min_score become NaN in every mode; adds the uint8 mask `rejected`.
-  speckle       engine.filter_speckles; adds the uint8 mask `speckles` of the cells removed.
-  fill          engine.fill_holes; adds the uint8 mask `holes` of the cells that were filled.
-  sgm           engine.sgm_refine on the two elevation planes: the cells are matched again
-                together, the candidates' costs and a smoothness term minimised along scan lines;
-                with sgm_where='filled' only the filled cells move and every other cell is an
-                anchor; adds `sgm_score` and the int8 `sgm_shift`.
-  refine        engine.photo_refine on the two elevation planes, of the filled cells only with
-                refine_where='filled'; adds `refine_score` and the int8 `refine_shift`.
-  lsm           engine.lsm_refine on the two elevation planes: the least-squares sub-pixel
-                step, of the filled cells only with lsm_where='filled'; adds `lsm_score` and
-                the int8 `lsm_status`.  With lsm_model='affine' or ('affine', max_shear) the
-                stage is engine.lsm_affine, which also solves for the stretch and shear of the
-                window, and adds the float64 `lsm_affine` [4][H][W] after them; its hook gets
-                max_shear after max_move and returns the affine planes as a fifth value.
-  smooth        engine.bilateral_filter, guided by img1 under the map's cells (smooth_guide
-                'image') or by the map itself ('self'); holes stay holes.
-  photo score   with photo=: adds `score`, the photo-consistency of the final d_map.
-
-The result is a tuple in the order of Chain.layout -- not the order the stages run in:
-(d_map, out_map[, err][, spread, count][, speckles][, holes][, sgm_score, sgm_shift]
-[, refine_score, refine_shift][, lsm_score, lsm_status[, lsm_affine]][[, rejected], score]).  A stage may be
-replaced by a host function (the hooks of solve_image_sharded); the calls are the ones written in
-the stage functions below.
+The caller stitches; every stage after that is optional, works on d_map [M = len(modes)][H][W] in place (on rank 0
+of a sharded solve) and is declared once, in the table below: its keywords with their defaults and parsers (None
+switches a stage off: nothing changes), the hook that replaces its device call by a host function, the tensors it
+adds to the result with the ImageCutSolver attributes they land in, and the function or functions that run it.
+RUN is the order the stages run in: stitch -> median -> photo reject -> speckle -> fill -> sgm -> refine -> lsm ->
+smooth -> photo score.  LAYOUT is the order of the result tuple -- not the order the stages run in:
+(d_map, out_map[, err][, spread, count][, speckles][, holes][, sgm_score, sgm_shift][, refine_score, refine_shift]
+[, lsm_score, lsm_status[, lsm_affine]][[, rejected], score]).  The table is read when a Chain is built or run; from
+it come the keywords Chain() takes, Chain.layout, the hooks Chain.run takes, the parsed attributes and the *_map
+attributes of ImageCutSolver, and the keywords and hooks of solve_image_sharded.  A new stage is one declaration
+and its place in RUN and LAYOUT.
 """
 
 from collections import namedtuple
@@ -43,10 +22,36 @@ import torch
 
 from deepmatching_stereo_matching_amd import engine
 
+f64, u8, i8 = torch.float64, torch.uint8, torch.int8
 
-def _median(c, v, r):
-    if c.median is None:
-        return
+# A tensor of the result.  name: its entry of Chain.layout; lead: the dimensions before [H][W] ('M': len(modes));
+# attr: the ImageCutSolver attribute it lands in, as bool when ``mask``; when(chain, consistency, merge): whether it
+# is there while its stage is on (None: always).
+Out = namedtuple('Out', 'name lead dtype attr mask when', defaults=(False, None))
+# key: the keyword that switches the stage on (None: the stitch); keywords: (name, default, parser) each, parsed in this
+# order; hook: the keyword of Chain.run that replaces the device call; run: its functions f(st, chain, v, r), one per
+# place in RUN; check(st, chain): what a stage that is on asks of the other keywords and the modes.
+Stage = namedtuple('Stage', 'key keywords hook run outs check', defaults=((), None))
+
+
+def _engine(parser, optional=True):
+    """The parser of a keyword by its name in engine, looked up when a Chain is built; None stays None."""
+    return lambda value: None if value is None and optional else getattr(engine, parser)(value)
+
+
+def _one_of(keyword, *allowed):
+    def parse(value):
+        if value not in allowed:
+            raise ValueError('%s must be %s' % (keyword, ' or '.join(map(repr, allowed))))
+        return value
+    return parse
+
+
+def _as_is(value):      # a `<key>_where`: checked against fill= by the stage that is on (_check_plane)
+    return value
+
+
+def _median(st, c, v, r):
     weight = engine.median_weight(c.median_weight, (v['d_map'], v['out_map']))
     if r.medianer is not None:
         v['d_map'] = r.medianer(v['d_map'], weight, *c.median)
@@ -54,8 +59,8 @@ def _median(c, v, r):
         v['d_map'] = engine.median_filter(v['d_map'], c.median[0], weight=weight, iters=c.median[1], out=v['d_map'])
 
 
-def _photo_reject(c, v, r):
-    if c.photo is None or c.photo[1] is None:
+def _photo_reject(st, c, v, r):
+    if c.photo[1] is None:
         return
     d = v['d_map']
     if r.photoer is not None:
@@ -65,9 +70,16 @@ def _photo_reject(c, v, r):
         v['d_map'], v['rejected'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, True)
 
 
-def _speckle(c, v, r):
-    if c.speckle is None:
-        return
+def _photo_score(st, c, v, r):
+    d = v['d_map']
+    if r.photoer is not None:
+        row, col = engine.photo_planes(c.modes)
+        v['score'] = r.photoer(r.img1, r.img2, d[row], d[col], c.photo[0], r.e, None, None)
+    else:
+        v['score'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, False)
+
+
+def _speckle(st, c, v, r):
     if r.speckler is not None:
         v['d_map'], v['speckles'] = r.speckler(v['d_map'], *c.speckle)
     else:
@@ -75,36 +87,21 @@ def _speckle(c, v, r):
                                                            return_removed=True)
 
 
-def _fill(c, v, r):
-    if c.fill is None:
-        return
+def _fill(st, c, v, r):
     if r.filler is not None:
         v['d_map'], v['holes'] = r.filler(v['d_map'], c.fill)
     else:
         v['d_map'], v['holes'] = engine.fill_holes(v['d_map'], c.fill, out=v['d_map'], return_holes=True)
 
 
-# The stages that match the two elevation planes again, in the order they run in.  key: the keyword (its
-# `<key>_where` keyword picks the cells, and the stage adds `<key>_score` [H][W]); hook: the keyword of Chain.run that
-# replaces it; stage: the engine function; aux: the int8 tensor it adds and the dimensions that precede [H][W].
-# Every hook is called as hook(img1, img2, d_row, d_col, p[0], p[1], e, *p[2:], mask) with p the parsed keyword.
-PlaneStage = namedtuple('PlaneStage', 'key hook stage aux lead')
-SGM = PlaneStage('sgm', 'sgmer', 'sgm_stage', 'sgm_shift', (2,))
-REFINE = PlaneStage('refine', 'refiner', 'refine_stage', 'refine_shift', (2,))
-LSM = PlaneStage('lsm', 'lsmer', 'lsm_stage', 'lsm_status', ())
-PLANE_STAGES = (SGM, REFINE, LSM)
-
-
-def _plane(st, c, v, r):
-    p = getattr(c, st.key)
-    if p is None:
-        return
+def _plane(stage, st, c, v, r, *scalars):
+    """A stage that matches the two elevation planes again: engine's ``stage``, or the hook, with the parsed keyword
+    and the ``scalars`` that follow it."""
+    p = getattr(c, st.key) + scalars
     d = v['d_map']
     holes = v['holes'] if getattr(c, st.key + '_where') == 'filled' else None
     hook = getattr(r, st.hook)
-    stage, outs = st.stage, [st.key + '_score', st.aux]
-    if st is LSM and c.lsm_model[0] == 'affine':      # max_shear follows max_move; the affine planes are one more result
-        p, stage, outs = p + (c.lsm_model[1],), 'lsm_affine_stage', outs + ['lsm_affine']
+    outs = [o.name for o in _outs(st, c)]
     if hook is not None:
         row, col = engine.refine_planes(c.modes)
         mask = None if holes is None else (np.asarray(holes[row]) | np.asarray(holes[col]))
@@ -116,12 +113,30 @@ def _plane(st, c, v, r):
     v.update(zip(outs, rest))
 
 
-_sgm, _refine, _lsm = (partial(_plane, st) for st in PLANE_STAGES)
+def _check_plane(st, c):
+    engine.refine_planes(c.modes)
+    engine.refine_where(getattr(c, st.key + '_where'), c.fill, st.key + '_where')
 
 
-def _smooth(c, v, r):
-    if c.smooth is None:
-        return
+def _affine(c, consistency=None, merge=None):
+    return c.lsm_model[0] == 'affine'
+
+
+def _lsm(st, c, v, r):
+    if _affine(c):      # max_shear follows max_move; the affine planes are one more result
+        _plane('lsm_affine_stage', st, c, v, r, c.lsm_model[1])
+    else:
+        _plane('lsm_stage', st, c, v, r)
+
+
+def _check_lsm(st, c):
+    _check_plane(st, c)
+    if _affine(c) and c.lsm[0] < 2:
+        raise ValueError('lsm radius must be in [2, 7] with lsm_model=\'affine\': nine taps cannot carry eight '
+                         'unknowns (got %r)' % (c.lsm[0],))
+
+
+def _smooth(st, c, v, r):
     d = v['d_map']
     if r.smoother is not None:
         H, W = np.shape(d)[-2:]
@@ -132,92 +147,160 @@ def _smooth(c, v, r):
         v['d_map'] = engine.bilateral_filter(d, *c.smooth, guide=guide, out=d)
 
 
-def _photo_score(c, v, r):
-    if c.photo is None:
-        return
-    d = v['d_map']
-    if r.photoer is not None:
-        row, col = engine.photo_planes(c.modes)
-        v['score'] = r.photoer(r.img1, r.img2, d[row], d[col], c.photo[0], r.e, None, None)
-    else:
-        v['score'] = engine.photo_stage(r.img1, r.img2, d, c.modes, c.photo, r.e, False)
+# The stitch of the caller, the head of the layout.  err [H][W]: with consistency=, the round-trip error; d_map is NaN
+# where it exceeds the tolerance.  With merge=: spread [M][H][W], max - min of the valid candidates of a pixel per
+# mode, and count [H][W], their number.
+STITCH = Stage(None, (), None, (), (
+    Out('d_map', ('M',), f64, 'd_map'), Out('out_map', (), f64, 'out_map'),
+    Out('err', (), f64, 'consistency_map', when=lambda c, consistency, merge: consistency is not None),
+    Out('spread', ('M',), f64, 'spread_map', when=lambda c, consistency, merge: merge is not None),
+    Out('count', (), u8, 'coverage_map', when=lambda c, consistency, merge: merge is not None)))
+
+# median: a radius, (radius,) or (radius, iters).  Runs first, immediately after the stitch, all modes in one call:
+# engine.median_filter, or medianer(d_map, weight or None, radius, iters) -> d_map.  median_weight: None -- the
+# unweighted median -- or 'correlation' -- weighted by the stitched out_map, shared by all modes.  Holes stay holes;
+# no tensor is added.
+MEDIAN = Stage('median', (('median', None, _engine('median_params')),
+                          ('median_weight', None, _one_of('median_weight', None, 'correlation'))),
+               'medianer', (_median,))
+
+# photo: a radius or (radius, min_score), the photo-consistency score: img2 is resampled where d_map claims the match
+# and correlated with img1 around the cell (engine.photo_score against the caller's pair, map cell (y, x) at image
+# pixel (y + e, x + e), e = (window_size - 1) // 2 of the solve).  Needs both 'elevation' and 'elevation2' in the
+# modes (else ValueError).  It runs last, after the smoothing, on the final d_map -- photoer(img1, img2, d_row, d_col,
+# radius, e, None, None) -> score -- and the float64 `score` [H][W] comes after every other tensor.  With a min_score
+# it also runs after the median and before the speckle filter: the cells that score below min_score become NaN in
+# every mode -- photoer(img1, img2, d_row, d_col, radius, e, min_score, d_map) -> (score, d_map, uint8 mask) -- and
+# the uint8 `rejected` [H][W] (the cells rejected, before any fill) comes immediately before the score.
+PHOTO = Stage('photo', (('photo', None, _engine('photo_params')),), 'photoer', (_photo_reject, _photo_score), (
+    Out('rejected', (), u8, 'photo_reject_map', True, lambda c, consistency, merge: c.photo[1] is not None),
+    Out('score', (), f64, 'photo_map')), lambda st, c: engine.photo_planes(c.modes))
+
+# speckle: (max_size, max_diff).  Removes the small segments of d_map before the fill, so the removed cells are filled
+# like any other hole: engine.filter_speckles, or speckler(d_map, max_size, max_diff) -> (filtered, uint8 mask).  Adds
+# the uint8 `speckles` [M][H][W] of the cells removed (before any fill).
+SPECKLE = Stage('speckle', (('speckle', None, _engine('speckle_params')),), 'speckler', (_speckle,),
+                (Out('speckles', ('M',), u8, 'speckle_map', True),))
+
+# fill: a count of Jacobi iterations per level.  Fills the holes of d_map -- the cells no tile covers and the ones that
+# consistency, photo and speckle rejected: engine.fill_holes, or filler(d_map, iters) -> (filled, uint8 mask).  Adds the
+# uint8 `holes` [M][H][W] of the cells that were filled; d_map is then dense.  out_map and err are never filled.
+FILL = Stage('fill', (('fill', None, _engine('fill_iterations')),), 'filler', (_fill,),
+             (Out('holes', ('M',), u8, 'hole_map', True),))
+
+# sgm, refine and lsm match the two elevation planes again and run after the fill and before the smoothing, in that
+# order.  Each needs both 'elevation' and 'elevation2' and no 'distance' in the modes (else ValueError).  `<key>_where`
+# picks the cells: 'all', or 'filled' -- only the cells the fill produced in either plane; needs fill=.  The hook is
+# called as hook(img1, img2, d_row, d_col, p[0], p[1], e, *p[2:], mask or None) with p the parsed keyword and returns
+# (d_row, d_col, score, the int8 tensor).  The stage adds the float64 `<key>_score` [H][W], the score of the position
+# kept (NaN: the cell was not matched again), and one int8 tensor.
+#
+# sgm: (radius, search, p1, p2) or (radius, search, p1, p2, paths), the semi-global re-matching (engine.sgm_refine, or
+# sgmer(..., radius, search, e, p1, p2, paths, mask)): the cells snap to integer positions and are matched again
+# together, the (2 search + 1)^2 candidates' costs and a smoothness term (p1 for a step of one pixel between
+# neighbouring cells, p2 for more, in score units) minimised along 4 or 8 scan directions.  With sgm_where='filled'
+# every other cell is a fixed anchor.  Kept as parsed, and handed to the hook so: the penalties as ints in units of
+# 1/1024.  Adds `sgm_score` and the int8 shift `sgm_shift` [2][H][W].
+SGM = Stage('sgm', (('sgm', None, _engine('sgm_params')), ('sgm_where', 'all', _as_is)), 'sgmer',
+            (partial(_plane, 'sgm_stage'),),
+            (Out('sgm_score', (), f64, 'sgm_score_map'), Out('sgm_shift', (2,), i8, 'sgm_shift_map')), _check_plane)
+
+# refine: (radius, search) or (radius, search, min_gain), the local re-matching (engine.photo_refine, or refiner(...,
+# radius, search, e, min_gain, mask)): a cell scores the (2 search + 1)^2 integer neighbours of the position it claims
+# and moves to the best one.  Adds `refine_score` and the int8 shift `refine_shift` [2][H][W].
+REFINE = Stage('refine', (('refine', None, _engine('refine_params')), ('refine_where', 'filled', _as_is)), 'refiner',
+               (partial(_plane, 'refine_stage'),),
+               (Out('refine_score', (), f64, 'refine_score_map'), Out('refine_shift', (2,), i8, 'refine_shift_map')),
+               _check_plane)
+
+# lsm: (radius, iters) or (radius, iters, max_move), the least-squares sub-pixel matching (engine.lsm_refine, or
+# lsmer(..., radius, iters, e, max_move, mask)): a cell solves iters times for the shift that best explains its img1
+# window and keeps it if the photo-consistency score rises.  Adds `lsm_score` and the int8 `lsm_status` [H][W] (iters:
+# accepted, 0: skipped, < 0: kept).  lsm_model: 'shift' (the default), 'affine' or ('affine', max_shear), validated
+# even when lsm is None.  With 'affine' the stage is engine.lsm_affine (radius >= 2), which also solves for the
+# stretch and shear of the window and so removes the bias of the shift on sloped terrain; the hook gets max_shear
+# after max_move and returns the affine planes as a fifth value, and the float64 `lsm_affine` [4][H][W] of (a, b, c,
+# d), NaN unless accepted, follows the status: -a and -d are the disparity gradients along the columns and the rows.
+LSM = Stage('lsm', (('lsm', None, _engine('lsm_params')), ('lsm_where', 'all', _as_is),
+                    ('lsm_model', 'shift', _engine('lsm_model_params', optional=False))), 'lsmer', (_lsm,),
+            (Out('lsm_score', (), f64, 'lsm_score_map'), Out('lsm_status', (), i8, 'lsm_status_map'),
+             Out('lsm_affine', (4,), f64, 'lsm_affine_map', when=_affine)), _check_lsm)
+
+# smooth: (radius, sigma_color, sigma_space).  Smooths d_map after the fill and the re-matching, all modes in one call:
+# engine.bilateral_filter, or smoother(d_map, guide or None, radius, sigma_color, sigma_space) -> d_map.  smooth_guide:
+# 'image' -- the guide is img1[e:e + H, e:e + W] as uint8, the pixel under each map cell -- or 'self': the map guides
+# itself.  Holes stay holes; no tensor is added.
+SMOOTH = Stage('smooth', (('smooth', None, _engine('smooth_params')),
+                          ('smooth_guide', 'image', _one_of('smooth_guide', 'image', 'self'))), 'smoother', (_smooth,))
+
+RUN = (MEDIAN, PHOTO, SPECKLE, FILL, SGM, REFINE, LSM, SMOOTH, PHOTO)      # PHOTO: its reject, then its score
+LAYOUT = (STITCH, SPECKLE, FILL, SGM, REFINE, LSM, PHOTO)
 
 
-STAGES = (_median, _photo_reject, _speckle, _fill, _sgm, _refine, _lsm, _smooth, _photo_score)
+def keywords():
+    """{keyword: (default, parser)} of the stages, in the order they are parsed."""
+    return {name: (default, parse) for st in dict.fromkeys(RUN) for name, default, parse in st.keywords}
+
+
+def hooks():
+    """The names of the hooks of the stages."""
+    return [st.hook for st in dict.fromkeys(RUN)]
+
+
+def outputs():
+    """Every Out the result can hold, in its order."""
+    return [o for st in LAYOUT for o in st.outs]
+
+
+def known(given, names, what):
+    """TypeError for the first of the keywords ``given`` that is not among ``names``."""
+    for name in given:
+        if name not in names:
+            raise TypeError('%s got an unexpected keyword argument %r' % (what, name))
+
+
+def _outs(st, c, consistency=None, merge=None):
+    """The tensors stage ``st`` adds under the chain ``c``."""
+    if st.key is not None and getattr(c, st.key) is None:
+        return []
+    return [o for o in st.outs if o.when is None or o.when(c, consistency, merge)]
 
 
 class Chain:
-    """The validated keywords of the chain (ValueError for a bad one) as attributes of their names,
-    parsed by engine.*_params: None switches a stage off."""
+    """The validated keywords of the chain (TypeError for an unknown one, ValueError for a bad one) as attributes
+    of their names, as their parsers leave them: None switches a stage off."""
 
-    def __init__(self, modes, fill=None, speckle=None, smooth=None, smooth_guide='image', median=None,
-                 median_weight=None, photo=None, refine=None, refine_where='filled', lsm=None, lsm_where='all',
-                 sgm=None, sgm_where='all', lsm_model='shift'):
+    def __init__(self, modes, **given):
+        table = keywords()
+        known(given, table, 'Chain()')
         self.modes = modes
-        self.fill = engine.fill_iterations(fill) if fill is not None else None
-        self.speckle = engine.speckle_params(speckle) if speckle is not None else None
-        self.smooth = engine.smooth_params(smooth) if smooth is not None else None
-        if smooth_guide not in ('image', 'self'):
-            raise ValueError("smooth_guide must be 'image' or 'self'")
-        self.smooth_guide = smooth_guide
-        self.median = engine.median_params(median) if median is not None else None
-        if median_weight not in (None, 'correlation'):
-            raise ValueError("median_weight must be None or 'correlation'")
-        self.median_weight = median_weight
-        self.photo = engine.photo_params(photo) if photo is not None else None
-        if self.photo is not None:
-            engine.photo_planes(modes)
-        for st, p, where in ((REFINE, refine, refine_where), (LSM, lsm, lsm_where), (SGM, sgm, sgm_where)):
-            p = getattr(engine, st.key + '_params')(p) if p is not None else None
-            setattr(self, st.key, p)
-            setattr(self, st.key + '_where', where)
-            if p is not None:
-                engine.refine_planes(modes)
-                engine.refine_where(where, self.fill, st.key + '_where')
-        self.lsm_model = engine.lsm_model_params(lsm_model)      # validated even when lsm is None
-        if self.lsm is not None and self.lsm_model[0] == 'affine' and self.lsm[0] < 2:
-            raise ValueError('lsm radius must be in [2, 7] with lsm_model=\'affine\': nine taps cannot carry eight '
-                             'unknowns (got %r)' % (self.lsm[0],))
+        for name, (default, parse) in table.items():
+            setattr(self, name, parse(given.get(name, default)))
+        for st in dict.fromkeys(RUN):
+            if st.check is not None and getattr(self, st.key) is not None:
+                st.check(st, self)
 
     def layout(self, H, W, consistency, merge):
         """The entries (name, shape, dtype) of the result tuple, in its order, for maps of H x W
         cells stitched with the ``consistency`` and ``merge`` keywords of the caller."""
         M = len(self.modes)
-        f64, u8 = torch.float64, torch.uint8
-        lay = [('d_map', (M, H, W), f64), ('out_map', (H, W), f64)]
-        if consistency is not None:
-            lay.append(('err', (H, W), f64))
-        if merge is not None:
-            lay += [('spread', (M, H, W), f64), ('count', (H, W), u8)]
-        if self.speckle is not None:
-            lay.append(('speckles', (M, H, W), u8))
-        if self.fill is not None:
-            lay.append(('holes', (M, H, W), u8))
-        for st in PLANE_STAGES:
-            if getattr(self, st.key) is not None:
-                lay += [(st.key + '_score', (H, W), f64), (st.aux, st.lead + (H, W), torch.int8)]
-                if st is LSM and self.lsm_model[0] == 'affine':
-                    lay.append(('lsm_affine', (4, H, W), f64))
-        if self.photo is not None:
-            if self.photo[1] is not None:
-                lay.append(('rejected', (H, W), u8))
-            lay.append(('score', (H, W), f64))
-        return lay
+        return [(o.name, tuple(M if n == 'M' else n for n in o.lead) + (H, W), o.dtype)
+                for st in LAYOUT for o in _outs(st, self, consistency, merge)]
 
     def names(self, consistency, merge):
         """The names of layout()."""
         return [name for name, _, _ in self.layout(0, 0, consistency, merge)]
 
-    def run(self, stitched, img1, img2, e, consistency, merge, medianer=None, photoer=None, speckler=None,
-            filler=None, refiner=None, smoother=None, lsmer=None, sgmer=None):
+    def run(self, stitched, img1, img2, e, consistency, merge, **given):
         """The stages over ``stitched``, the tensors of the stitch: the head of the layout, a merge
         of one direction without its err -> the result tuple.  ``img1``, ``img2``: the pair as the
         caller got it (never the stacked one of a two-direction solve); ``e``: the offset of a map
-        cell in the image; a hook replaces the device stage of its name (None: the device stage)."""
+        cell in the image; a hook (hooks()) replaces the device stage of its name (None: the device stage)."""
+        known(given, hooks(), 'Chain.run()')
         names = self.names(consistency, merge)
         v = dict(zip(names, stitched))
-        r = SimpleNamespace(img1=img1, img2=img2, e=int(e), medianer=medianer, photoer=photoer, speckler=speckler,
-                            filler=filler, refiner=refiner, smoother=smoother, lsmer=lsmer, sgmer=sgmer)
-        for stage in STAGES:
-            stage(self, v, r)
+        r = SimpleNamespace(img1=img1, img2=img2, e=int(e), **{**dict.fromkeys(hooks()), **given})
+        for i, st in enumerate(RUN):
+            if getattr(self, st.key) is not None:
+                st.run[RUN[:i].count(st)](st, self, v, r)
         return tuple(v[name] for name in names)

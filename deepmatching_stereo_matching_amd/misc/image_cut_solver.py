@@ -31,24 +31,11 @@ class ImageCutSolver():
         filtering_num=3,
         filtering_mode='average',
         consistency=None,
-        fill=None,
         merge=None,
         merge_min_count=1,
-        speckle=None,
-        smooth=None,
-        smooth_guide='image',
-        median=None,
-        median_weight=None,
-        photo=None,
-        refine=None,
-        refine_where='filled',
         prior=None,
         coarse=None,
-        lsm=None,
-        lsm_where='all',
-        sgm=None,
-        sgm_where='all',
-        lsm_model='shift'
+        **keywords
     ):
         self.img_shape = img1.shape
         assert self.img_shape == img2.shape, '2枚の画像は同じサイズ！'
@@ -83,59 +70,19 @@ class ImageCutSolver():
         self.filtering_mode = filtering_mode
         # forward-backward consistency tolerance in pixels (None: the reference's behaviour)
         self.consistency = consistency
-        self.consistency_map = None
         # rule that merges the overlapping tiles of a pixel (engine.stitch_merge); None: the last tile wins
         if merge is not None:
             engine.merge_rule(merge)
         self.merge = merge
         self.merge_min_count = merge_min_count
-        self.coverage_map = None
-        self.spread_map = None
-        # The post-processing of the stitched d_map (chain.py has the stages and their order); every
-        # keyword is kept as parsed, None: the stage is off.
-        #   fill: Jacobi iterations of the hole fill; hole_map marks the cells that were filled
-        #   speckle: (max_size, max_diff) of the speckle filter; speckle_map marks the cells removed
-        #   smooth: (radius, sigma_color, sigma_space) of the bilateral smoothing; smooth_guide: 'image'
-        #       (img1 under the map's cells, uint8) or 'self' (the map guides itself)
-        #   median: radius, (radius,) or (radius, iters) of the median filter; median_weight: None
-        #       (unweighted) or 'correlation' (weighted by out_map)
-        #   photo: radius or (radius, min_score) of the photo-consistency score: img2 is resampled where
-        #       d_map claims the match and correlated with img1 around the cell.  photo_map is the score of
-        #       the final d_map; with min_score the cells scoring below it are also rejected (NaN in every
-        #       mode) and photo_reject_map marks them.  Needs 'elevation' and 'elevation2' in degree_map_mode
-        #   refine: (radius, search) or (radius, search, min_gain) of the local re-matching: a cell scores the
-        #       (2 search + 1)^2 integer neighbours of the position it claims and moves to the best one.
-        #       refine_where: 'filled' (only the cells the fill produced; needs fill=) or 'all'.  Needs
-        #       'elevation' and 'elevation2' and no 'distance' in degree_map_mode.  refine_score_map is the
-        #       score of the position kept (NaN: not refined), refine_shift_map the int8 shift [2][H][W]
-        #   lsm: (radius, iters) or (radius, iters, max_move) of the least-squares sub-pixel matching after
-        #       the refine stage: a cell solves iters times for the shift that best explains its img1 window
-        #       and keeps it if the photo-consistency score rises.  lsm_where: 'all' or 'filled' (needs
-        #       fill=).  The modes as for refine.  lsm_score_map is the score of the position kept (NaN: not
-        #       scored), lsm_status_map the int8 status [H][W] (iters: accepted, 0: skipped, < 0: kept)
-        #   lsm_model: 'shift' (the default), 'affine' or ('affine', max_shear): with 'affine' the lsm stage also
-        #       solves for the stretch and shear of the window (engine.lsm_affine; radius >= 2), which removes the
-        #       bias of the shift on sloped terrain.  lsm_affine_map is then the float64 [4][H][W] of (a, b, c, d),
-        #       NaN unless accepted: -a and -d are the disparity gradients along the columns and the rows
-        #   sgm: (radius, search, p1, p2) or (radius, search, p1, p2, paths) of the semi-global re-matching after
-        #       the fill and before the refine stage: the cells snap to integer positions and are matched again
-        #       together, the (2 search + 1)^2 candidates' costs and a smoothness term (p1 for a step of one pixel
-        #       between neighbouring cells, p2 for more, in score units) minimised along 4 or 8 scan directions.
-        #       sgm_where: 'all' or 'filled' (needs fill=; every other cell is then a fixed anchor).  The modes as
-        #       for refine.  sgm_score_map is the score of the position kept (NaN: not matched), sgm_shift_map the
-        #       int8 shift [2][H][W].  Kept as parsed: the penalties in units of 1/1024
-        self.chain = chain.Chain(degree_map_mode, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide,
-                                 median=median, median_weight=median_weight, photo=photo, refine=refine,
-                                 refine_where=refine_where, lsm=lsm, lsm_where=lsm_where, sgm=sgm,
-                                 sgm_where=sgm_where, lsm_model=lsm_model)
-        self._sgm_given = sgm      # the shard path parses the keyword itself: it gets what this solver was given
-        for name in ('fill', 'speckle', 'smooth', 'smooth_guide', 'median', 'median_weight', 'photo', 'refine',
-                     'refine_where', 'lsm', 'lsm_where', 'sgm', 'sgm_where', 'lsm_model'):
+        # The post-processing of the stitched d_map: chain.py declares the stages, their keywords (which arrive
+        # here as **keywords), their order and the *_map attributes their tensors land in.  Every keyword is kept
+        # as parsed (None: the stage is off); every *_map is None until the solve.
+        self.chain = chain.Chain(degree_map_mode, **keywords)
+        for name in chain.keywords():
             setattr(self, name, getattr(self.chain, name))
-        self.hole_map = self.speckle_map = self.photo_map = self.photo_reject_map = None
-        self.refine_score_map = self.refine_shift_map = None
-        self.lsm_score_map = self.lsm_status_map = self.lsm_affine_map = None
-        self.sgm_score_map = self.sgm_shift_map = None
+        for o in chain.outputs():
+            setattr(self, o.attr, None)
         # Disparity priors (engine.solve_tiles_prior): tile t's crop of img2 is cut at its origin minus
         # the expected disparity, so that a match outside the tile's own window of img2 can be found.
         #   prior: (d2, d1) ints, one expected ('elevation2', 'elevation') for every tile, in the units and
@@ -218,9 +165,9 @@ class ImageCutSolver():
         With self.merge set the stitch is engine.stitch_merge (both directions when
         self.consistency is set) and the spread and the uint8 count of valid candidates follow
         out_map / the error.  The stitched d_map then runs through self.chain (chain.py: the stages
-        that self.fill, self.speckle, self.smooth, self.median, self.photo, self.sgm, self.refine and self.lsm switch on,
-        against self.img1 / self.img2 with e = exclusive_pix), which appends the tensors of its
-        stages: the tuple is the one chain.Chain.layout names."""
+        its keywords switch on, against self.img1 / self.img2 with e = exclusive_pix), which appends the
+        tensors of its stages: the tuple is the one chain.Chain.layout names.  The sharded branch is handed
+        self.chain itself, so no keyword is parsed a second time."""
         from deepmatching_stereo_matching_amd import shard
         n = list(self.len)
         if n[0] < 1 or n[1] < 1:
@@ -238,15 +185,9 @@ class ImageCutSolver():
                                              self.sub_pix, self.filtering, self.filtering_window_size,
                                              self.filtering_num, self.filtering_mode,
                                              result=shard.shard_result(), grid=(n, origins),
-                                             consistency=self.consistency, fill=self.fill,
-                                             merge=self.merge, merge_min_count=self.merge_min_count,
-                                             speckle=self.speckle, smooth=self.smooth,
-                                             smooth_guide=self.smooth_guide, median=self.median,
-                                             median_weight=self.median_weight, photo=self.photo,
-                                             refine=self.refine, refine_where=self.refine_where,
-                                             lsm=self.lsm, lsm_where=self.lsm_where, lsm_model=self.lsm_model,
-                                             sgm=self._sgm_given, sgm_where=self.sgm_where,
-                                             prior=self.prior, coarse=self.coarse)
+                                             consistency=self.consistency, merge=self.merge,
+                                             merge_min_count=self.merge_min_count, prior=self.prior,
+                                             coarse=self.coarse, chain=self.chain)
         if self.prior is not None or self.coarse is not None:
             maps = self._stitch_prior(args, n, origins)
         else:
@@ -284,29 +225,15 @@ class ImageCutSolver():
             maps += (engine.stitch(torch.stack([err, err, err], 1), n, h0, w0, self.stride, ['elevation'])[1],)
         return maps
 
-    # attribute: (entry of chain.Chain.layout, a uint8 mask that is kept as bool)
-    _MAPS = {'d_map': ('d_map', False), 'out_map': ('out_map', False),
-             'consistency_map': ('err', False),        # round-trip error; d_map is NaN where it exceeds the tolerance
-             'spread_map': ('spread', False),          # max - min of the valid candidates of a pixel, per mode
-             'coverage_map': ('count', False),         # their number
-             'speckle_map': ('speckles', True),        # the cells the speckle filter removed (before any fill)
-             'hole_map': ('holes', True),              # d_map is dense; the cells that were filled
-             'sgm_score_map': ('sgm_score', False), 'sgm_shift_map': ('sgm_shift', False),
-             'refine_score_map': ('refine_score', False), 'refine_shift_map': ('refine_shift', False),
-             'lsm_score_map': ('lsm_score', False), 'lsm_status_map': ('lsm_status', False),
-             'lsm_affine_map': ('lsm_affine', False),
-             'photo_reject_map': ('rejected', True),   # the cells scoring below min_score (before any fill)
-             'photo_map': ('score', False)}
-
     def _execute_matching(self):
         """
         小画像ごとにマッチングを行い結果を結合
         """
         maps = dict(zip(self.chain.names(self.consistency, self.merge), self._execute_matching_device()))
-        for attr, (name, mask) in self._MAPS.items():
-            t = maps.get(name)      # absent: the stage is off; None: off rank 0 with tile_sharding(result='root')
+        for o in chain.outputs():
+            t = maps.get(o.name)      # absent: the stage is off; None: off rank 0 with tile_sharding(result='root')
             a = t.cpu().numpy() if t is not None else None
-            setattr(self, attr, a.astype(bool) if mask and a is not None else a)
+            setattr(self, o.attr, a.astype(bool) if o.mask and a is not None else a)
         if self._prior_dev is not None:
             q_eff, valid = self._prior_dev
             n0, n1 = self.len

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import chain, engine
+from . import chain as chains, engine
 
 # Tile sharding of the mirror ImageCutSolver is OPT-IN: a process group alone does not turn it
 # on (ranks that each solve their own pairs, solve_pairs_sharded, must not enter one
@@ -381,13 +381,9 @@ def solve_tiles_sharded(img1, img2, origins, h0, w0, ws, method, sub_pix=True, f
 
 def solve_image_sharded(img1, img2, image_size, stride, window_size, method, modes=('elevation',),
                         sub_pix=True, filtering=False, filter_window_size=3, filtering_num=3,
-                        filtering_mode='average', device=None, solver=None, stitcher=None,
-                        result='all', chunks=4, grid=None, consistency=None, fill=None, filler=None,
-                        merge=None, merge_min_count=1, merger=None, speckle=None, speckler=None,
-                        smooth=None, smooth_guide='image', smoother=None, median=None, median_weight=None,
-                        medianer=None, photo=None, photoer=None, refine=None, refine_where='filled',
-                        refiner=None, prior=None, coarse=None, lsm=None, lsm_where='all', lsmer=None,
-                        sgm=None, sgm_where='all', sgmer=None, lsm_model='shift'):
+                        filtering_mode='average', device=None, solver=None, stitcher=None, merger=None,
+                        result='all', chunks=4, grid=None, consistency=None, merge=None, merge_min_count=1,
+                        prior=None, coarse=None, chain=None, **post):
     """ImageCutSolver()() for one (large) pair with its tiles sharded over the ranks
     (BandSolver), stitched on rank 0 -> (d_map [len(modes)][H][W], out_map [H][W]) on every rank
     (``result='all'``: one broadcast of the stitched maps from rank 0) or on rank 0 only
@@ -399,69 +395,18 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
     0 splits the gathered tiles and stitches with the forward-backward check fused in
     (engine.stitch_fb, or ``stitcher(fwd, bwd, n, h0, w0, stride, modes, tol)``) ->
     (d_map, out_map, err [H][W]) under the same ``result`` rules ((None, None, None) off root).
-    ``fill``: a count of Jacobi iterations; rank 0 then fills the holes of the stitched d_map
-    (the cells no tile covers and, with ``consistency``, the rejected ones) right after it
-    stitches (engine.fill_holes, or ``filler(d_map, iters) -> (filled, uint8 mask)``), and the
-    tuple gains the uint8 hole mask [len(modes)][H][W] as its LAST element, under the same
-    ``result`` rules.  out_map and err are never filled.  None: nothing changes.
     ``merge``: a rule name ('last', 'center', 'feather', 'median'); rank 0 then merges every
     covering tile of a pixel instead of keeping the last (engine.stitch_merge with
     ``merge_min_count``, both directions when ``consistency`` is set, or ``merger(fwd, bwd or
     None, n, h0, w0, stride, modes, tol or None, rule, min_count) -> (d_map, out_map, err or None,
     spread, count)``) and the tuple is (d_map, out_map[, err], spread [len(modes)][H][W], count
-    [H][W] uint8[, holes]); the hole mask stays last.  None: nothing changes.
-    ``speckle``: a (max_size, max_diff) pair; rank 0 then removes the small segments of the
-    stitched d_map after the stitch and before the fill (engine.filter_speckles, or
-    ``speckler(d_map, max_size, max_diff) -> (filtered, uint8 mask)``), so the removed cells are
-    filled like any other hole, and the tuple gains the uint8 mask [len(modes)][H][W] of the
-    cells removed immediately before the hole mask: (d_map, out_map[, err][, spread, count]
-    [, speckles][, holes]).  None: nothing changes.
-    ``smooth``: a (radius, sigma_color, sigma_space) triple; rank 0 then smooths d_map last, after
-    the fill, all modes in one call (engine.bilateral_filter, or ``smoother(d_map, guide or None,
-    radius, sigma_color, sigma_space) -> d_map``).  ``smooth_guide``: 'image' -- the guide is
-    img1[e:e + H, e:e + W] as uint8, e = (window_size - 1) // 2, the pixel under each map cell
-    -- or 'self'.  Holes stay holes; no tensor is added.  None: nothing changes.
-    ``median``: a radius, (radius,) or (radius, iters); rank 0 then median filters d_map first,
-    immediately after the stitch and before the speckle filter, the fill and the smoothing, all
-    modes in one call (engine.median_filter, or ``medianer(d_map, weight or None, radius, iters) ->
-    d_map``).  ``median_weight``: None -- the unweighted median -- or 'correlation' -- weighted by
-    the stitched out_map, shared by all modes.  Holes stay holes; no tensor is added.  None:
-    nothing changes.
-    ``photo``: a radius or (radius, min_score), with both 'elevation' and 'elevation2' in ``modes``
-    (else ValueError); rank 0 then scores the final d_map last, after the smoothing
-    (engine.photo_score against img1 / img2 with the offset e, or ``photoer(img1, img2, d_row, d_col,
-    radius, e, None, None) -> score``) and the float64 score [H][W] is appended after every other
-    tensor.  With a min_score rank 0 first rejects the cells that score below it in every mode,
-    after the median and before the speckle filter (``photoer(img1, img2, d_row, d_col, radius, e,
-    min_score, d_map) -> (score, d_map, uint8 mask)``), and the uint8 mask [H][W] comes immediately
-    before the score: (d_map, out_map[, err][, spread, count][, speckles][, holes][[, rejected],
-    score]).  None: nothing changes.
-    ``refine``: (radius, search) or (radius, search, min_gain), with both 'elevation' and 'elevation2'
-    and no 'distance' in ``modes`` (else ValueError); rank 0 then matches the cells again locally after
-    the fill and before the smoothing (engine.photo_refine with the offset e, or ``refiner(img1, img2,
-    d_row, d_col, radius, search, e, min_gain, mask or None) -> (d_row, d_col, score, int8 shift
-    [2][H][W])``).  ``refine_where``: 'filled' -- only the cells the fill produced in either plane;
-    needs ``fill`` -- or 'all'.  The float64 score [H][W] and the shift come immediately before the
-    photo tensors: (d_map, out_map[, err][, spread, count][, speckles][, holes][, refine score, refine
-    shift][, lsm score, lsm status][[, rejected], score]).  None: nothing changes.
-    ``lsm``: (radius, iters) or (radius, iters, max_move), the modes as for ``refine``; rank 0 then
-    runs the least-squares sub-pixel matching after the refine stage and before the smoothing
-    (engine.lsm_refine with the offset e, or ``lsmer(img1, img2, d_row, d_col, radius, iters, e,
-    max_move, mask or None) -> (d_row, d_col, score, int8 status [H][W])``).  ``lsm_where``: 'all' or
-    'filled' (needs ``fill``).  The float64 score [H][W] and the status come immediately after the
-    refine tensors.  None: nothing changes.  ``lsm_model``: 'shift' (the default: today's stage, bit for
-    bit), 'affine' or ('affine', max_shear): engine.lsm_affine, radius >= 2, or ``lsmer(img1, img2, d_row,
-    d_col, radius, iters, e, max_move, max_shear, mask or None) -> (d_row, d_col, score, status, float64
-    affine [4][H][W])``; the affine planes follow the status.  Validated even when ``lsm`` is None.
-    ``sgm``: (radius, search, p1, p2) or (radius, search, p1, p2, paths), the modes as for ``refine``;
-    rank 0 then matches the cells again together after the fill and before the refine stage
-    (engine.sgm_refine with the offset e, or ``sgmer(img1, img2, d_row, d_col, radius, search, e, p1,
-    p2, paths, mask or None) -> (d_row, d_col, score, int8 shift [2][H][W])`` with the penalties as
-    ints in units of 1/1024).  ``sgm_where``: 'all' or 'filled' (needs ``fill``; every other cell is
-    then a fixed anchor).  The float64 score [H][W] and the shift come immediately before the refine
-    tensors.  None: nothing changes.
-    The stages after the stitch, their order and the layout of the tuple are chain.py's (its module
-    docstring states the order once); a hook replaces the device stage of its name there.
+    [H][W] uint8).  None: nothing changes.
+    ``**post``: the keywords of the stages that rank 0 runs on the stitched d_map (``fill=``, ``photo=``,
+    ...) and the hooks that replace a stage by a host function (``filler=``, ``photoer=``, ...).  chain.py
+    declares them, with the order of the stages and the layout of the tuple, whose tensors follow the
+    stitch's under the same ``result`` rules; an unknown name is a TypeError.  ``chain``: a chain.Chain
+    built by the caller in place of the stage keywords (ImageCutSolver passes its own, so that no
+    keyword is parsed twice): its modes must be ``modes``, and stage keywords beside it are a ValueError.
     ``prior``, ``coarse``: ImageCutSolver's disparity priors; not None raises ValueError -- the bands
     solve their tiles at one origin in both images."""
     for name, value in (('prior=', prior), ('coarse=', coarse)):
@@ -469,9 +414,14 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
             raise ValueError('%s not supported with tile sharding' % name)
     if result not in ('all', 'root'):
         raise ValueError("result must be 'all' or 'root'")
-    post = chain.Chain(modes, fill=fill, speckle=speckle, smooth=smooth, smooth_guide=smooth_guide, median=median,
-                       median_weight=median_weight, photo=photo, refine=refine, refine_where=refine_where,
-                       lsm=lsm, lsm_where=lsm_where, sgm=sgm, sgm_where=sgm_where, lsm_model=lsm_model)
+    chains.known(post, list(chains.keywords()) + chains.hooks(), 'solve_image_sharded()')
+    hooks = {name: post.pop(name) for name in chains.hooks() if name in post}
+    if chain is None:
+        chain = chains.Chain(modes, **post)
+    elif post:
+        raise ValueError('chain= already holds the stage keywords: %s cannot be passed beside it' % ', '.join(post))
+    elif list(chain.modes) != list(modes):
+        raise ValueError('chain= was built for the modes %r, not %r' % (list(chain.modes), list(modes)))
     pair = img1, img2      # what the stages read (consistency stacks the pair below)
     if merge is not None:
         engine.merge_rule(merge)
@@ -490,14 +440,12 @@ def solve_image_sharded(img1, img2, image_size, stride, window_size, method, mod
         fwd, bwd = (match[:T], match[T:]) if consistency is not None else (match, None)
         maps = engine.stitch_any(fwd, bwd, n, image_size[0], image_size[1], stride, list(modes), consistency, merge,
                                  merge_min_count, stitcher=stitcher, merger=merger)
-        maps = post.run(maps, pair[0], pair[1], (window_size - 1) // 2, consistency, merge, filler=filler,
-                        speckler=speckler, smoother=smoother, medianer=medianer, photoer=photoer, refiner=refiner,
-                        lsmer=lsmer, sgmer=sgmer)
+        maps = chain.run(maps, pair[0], pair[1], (window_size - 1) // 2, consistency, merge, **hooks)
     if not _group() or world()[1] == 1:
         return maps
     H = stride[0] * (n[0] - 1) + image_size[0]
     W = stride[1] * (n[1] - 1) + image_size[1]
-    layout = post.layout(H, W, consistency, merge)
+    layout = chain.layout(H, W, consistency, merge)
     if result == 'root':
         return maps if maps is not None else (None,) * len(layout)
     if maps is None:

@@ -518,8 +518,8 @@ def test_chain_layout_and_names():
                                        'rejected', 'score']
     assert chain_mod.Chain(PMODES, sgm=SGM, photo=2).names(None, None) == ['d_map', 'out_map', 'sgm_score', 'sgm_shift',
                                                                           'score']
-    assert chain_mod.STAGES.index(chain_mod._fill) + 1 == chain_mod.STAGES.index(chain_mod._sgm) == \
-        chain_mod.STAGES.index(chain_mod._refine) - 1
+    assert chain_mod.RUN.index(chain_mod.FILL) + 1 == chain_mod.RUN.index(chain_mod.SGM) == \
+        chain_mod.RUN.index(chain_mod.REFINE) - 1
     # sgm=None: the layouts of the parent, entry for entry
     for kw in (dict(), dict(fill=4), dict(fill=4, refine=(2, 1), lsm=(2, 2), photo=(2, 0.75))):
         assert chain_mod.Chain(PMODES, sgm=None, **kw).layout(3, 4, 1.0, None) == \
@@ -545,11 +545,18 @@ def test_sgm_keyword():
     kw = dict(image_size=[16, 16], stride=[12, 16], degree_map_mode=list(PMODES))
     s = ImageCutSolver(a, b, sgm=SGM, **kw)
     assert s.sgm == (2, 2, 2048, 8192, 8) and s.sgm_where == 'all' and s.sgm_score_map is None and s.sgm_shift_map is None
-    assert s._sgm_given == SGM and engine.sgm_params(s._sgm_given) == s.sgm      # what the shard path is handed
+    got = []      # what the shard path is handed: the solver's own chain, and no chain keyword
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(shard, 'tile_sharding_enabled', lambda: True)
+        mp.setattr(shard, 'solve_image_sharded', lambda *args, **kwargs: got.append(kwargs))
+        s._execute_matching_device()
+    assert got[0]['chain'] is s.chain and s.chain.sgm == (2, 2, 2048, 8192, 8)
+    assert not set(got[0]) & (set(chain_mod.keywords()) | set(chain_mod.hooks()))
     assert ImageCutSolver(a, b, sgm=(3, 1, 0.5, 0.5, 4), sgm_where='filled', fill=4, **kw).sgm == (3, 1, 512, 512, 4)
     s = ImageCutSolver(a, b, **kw)
-    assert s.sgm is None and s.sgm_score_map is None and s.sgm_shift_map is None and s._sgm_given is None
-    assert 'sgm_score_map' in ImageCutSolver._MAPS and ImageCutSolver._MAPS['sgm_shift_map'] == ('sgm_shift', False)
+    assert s.sgm is None and s.sgm_score_map is None and s.sgm_shift_map is None and s.chain.sgm is None
+    maps = {o.attr: (o.name, o.mask) for o in chain_mod.outputs()}
+    assert 'sgm_score_map' in maps and maps['sgm_shift_map'] == ('sgm_shift', False)
     with pytest.raises(ValueError):
         ImageCutSolver(a, b, sgm=SGM, **dict(kw, degree_map_mode=['elevation', 'elevation2', 'distance']))
     with pytest.raises(ValueError):
